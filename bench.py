@@ -11,17 +11,23 @@ CABAC bit counts -- the composed walk's ~7 000 / ~11 000 launches per lockstep C
 since round 6), ONE fused kernel per step with --walk fused or presets slow / placebo: xeve_amd/csrc/walk.h), entropy writer, loop filter, second writer pass, padding, parameter sets + SEI + slice NAL units.  Sixty-four GOPs (--seeded) spread over every batch of rank 0 (its first and last among them) are the reference's own seed-4 input.
 
 BOUNDED.  A whole 8-frame 3840x2160 job is 8 x 302 lockstep steps of a few hundred ms each whatever the batch size (a CTU's mode decision is a serial chain; the width is in
-the GOPs) -- a quarter of an hour.  The bench therefore runs the job's first --pictures pictures in coding order (default 3: the IDR picture and the first two B
-pictures) and stops; what GOP 0 has produced by then is checked byte for byte against the PREFIX of the reference's bitstream that ends with the same picture
-(tests/golden/cfg4_8f_v1.json, recorded from the unmodified reference application; the WHOLE 8-frame GOP is pinned by tests/test_enc_gpu.py on the same library).
---pictures 0 runs the whole job.
+the GOPs) -- a quarter of an hour.  The bench therefore runs the job's first W + K bench steps and stops.
 
-A STEP.  The steps that are run are cut into W + K equal slices: the first W are the untimed warm-up, the K others are timed between device fences + barriers.  `value` =
-frames coded inside the timed slices (GOPs x the timed share of a picture's steps) / the timed seconds, over all ranks.  With the driver's K = 20, W = 5 and 3 pictures the
-timed region is the last 40 % of the IDR picture and two whole B pictures (IDR share 17 %; 12.5 % in a whole GOP, and an IDR step is the cheaper one: the figure is within a
-few per cent of the whole-GOP rate, `config.timed_picture_mix` says exactly what was timed).  Every rank encodes its own GOPs ("weak"); no collective in the data path.
+A STEP.  One bench step is a fixed share of the job: step_ctus() lockstep CTU steps, 3/25 of a picture's (36 at 3840x2160), whatever --steps and --warmup say.  The first W
+steps are the untimed warm-up, the K others are timed between device fences + barriers; `ms_per_step` = the timed seconds / K.  `value` = frames coded inside the timed steps
+(GOPs x the timed share of a picture's steps) / the timed seconds, over all ranks.  With the driver's K = 20, W = 5 the timed region is the last 40 % of the IDR picture and
+almost two whole B pictures (IDR share 17 %; 12.5 % in a whole GOP, and an IDR step is the cheaper one: the figure is within a few per cent of the whole-GOP rate,
+`config.timed_picture_mix` says exactly what was timed).  W + K may not run past the end of the GOP (67 steps at 3840x2160).  Every rank encodes its own GOPs ("weak"); no
+collective in the data path.
 
-The JSON line also carries
+A plain run does only that and prints the line (metric, value, unit, ms_per_step, dtype, config, encode).  --dump-outputs DIR runs the job on, untimed, to the end of the
+picture the timed steps left part way and writes what they produced (dump_outputs(): the GOPs' bitstreams) as DIR/*.npy; the inputs are the same from run to run.
+
+--full adds, after the timed steps, the job run on (untimed) to the end of picture --pictures (default 3: the IDR picture and the first two B pictures), GOP 0's bitstream
+checked byte for byte against the PREFIX of the reference's bitstream that ends with the same picture (tests/golden/cfg4_8f_v1.json, recorded from the unmodified reference
+application; the WHOLE 8-frame GOP is pinned by tests/test_enc_gpu.py on the same library; --pictures 0 runs the whole GOP), and the extras below.
+
+With --full the JSON line also carries
   roofline     : the SAD kernel of the path = k_me_epzs (composed walk; with the fused walk k_walk, the whole CTU mode decision of a step in one launch): the motion search's
                  SAD work (sample pairs counted on the device) over the kernel's HIP-event time on its own stream, against the VALU roof for v_sad_u16, with BASELINE's
                  algorithmic-bytes-over-HBM-peak figure and the PMC HBM traffic (profiles/r04_*_pmc.json) as secondary keys; `by_time` = the class that owns the GPU time:
@@ -225,8 +231,61 @@ def check_prefix(stream, gold):
     return 0
 
 
-def run_job(a, torch, dist, dev, rank, world, W, H, label, with_cpu):
-    """one bounded encode at W x H; returns the result record (rank 0) or None"""
+def step_ctus(per_picture):
+    """lockstep CTU steps in one bench step: 3/25 of a picture's (36 at 3840x2160) -- the slice the driver's --steps 20 --warmup 5 cut from the first three pictures
+    before a step became a fixed unit -- whatever --steps and --warmup say"""
+    return max(1, 3 * per_picture // 25)
+
+
+def pictures_done(run_steps, per_picture):
+    """(the pictures the first run_steps lockstep steps reach into, the steps still to issue to finish the last of them): --dump-outputs runs the job on, untimed, by
+    that many steps, so that the picture the timed steps left part way is in the dump and a dump always holds at least one whole picture"""
+    P = max(1, -(-run_steps // per_picture))
+    return P, P * per_picture - run_steps
+
+
+# the GOPs whose bitstreams --dump-outputs samples: GOP 0 and 15 others drawn once from GOPs 1 .. 255, whatever the batch size (those beyond it are left out)
+DUMP_SAMPLE_GOPS = [0] + sorted(np.random.default_rng(20261016).choice(np.arange(1, 256), size=15, replace=False).tolist())
+
+
+def dump_outputs(out_dir, encs, gops_per_batch, pictures):
+    """what the timed path has produced, once the picture its last step left part way is finished: every GOP's bitstream (xeve_hip_enc_flush), written as float arrays
+    -- the byte count and byte sum of every GOP (GOPs of all batches in order), and of the sample GOPs (DUMP_SAMPLE_GOPS) the CRC-32 of the whole bitstream and its bytes
+    at 2^18 fixed, seeded positions -- 17 MB at most; beside them the pictures they hold and the GOPs of every batch (the batch sizes follow the free HBM)"""
+    import zlib
+
+    if pictures < 1:
+        raise RuntimeError("bench.py --dump-outputs: the dump would hold no whole picture")
+    for e in encs:
+        e.flush()
+    where = [(e, g) for e, n in zip(encs, gops_per_batch) for g in range(n)]
+    pick = [g for g in DUMP_SAMPLE_GOPS if g < len(where)]
+    u = np.random.default_rng(20261017).random(1 << 18)
+    sizes, sums = np.zeros(len(where), np.float64), np.zeros(len(where), np.float64)
+    crc, sample = np.zeros(len(pick), np.float64), np.zeros((len(pick), 1 << 18), np.float32)
+    for i, (e, g) in enumerate(where):
+        b = e.bitstream(g)
+        if not b:
+            raise RuntimeError("bench.py --dump-outputs: GOP %d has no bitstream after %d pictures" % (i, pictures))
+        v = np.frombuffer(b, dtype=np.uint8)
+        sizes[i], sums[i] = len(b), v.sum(dtype=np.uint64)
+        if i in pick:
+            k = pick.index(i)
+            crc[k] = zlib.crc32(b)
+            sample[k] = v[(u * len(b)).astype(np.int64)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "bitstream_bytes.npy"), sizes)
+    np.save(os.path.join(out_dir, "bitstream_byte_sum.npy"), sums)
+    np.save(os.path.join(out_dir, "bitstream_sample_gops.npy"), np.array(pick, np.float64))
+    np.save(os.path.join(out_dir, "bitstream_sample_crc32.npy"), crc)
+    np.save(os.path.join(out_dir, "bitstream_sample.npy"), sample)
+    np.save(os.path.join(out_dir, "pictures.npy"), np.array([pictures], np.float64))
+    np.save(os.path.join(out_dir, "gops_per_batch.npy"), np.array(gops_per_batch, np.float64))
+
+
+def run_job(a, torch, dist, dev, rank, world, W, H, label, with_cpu, full=True, dump_dir=None):
+    """one bounded encode at W x H: the --warmup + --steps bench steps of step_ctus() lockstep CTU steps each; returns the result record (rank 0) or None.
+    full (--full): the roofline's HIP-event timers in the timed region and, after it, the job run on to the end of picture --pictures and checked against the golden"""
     from xeve_amd import encode, lib
 
     F, T = a.frames, a.threads
@@ -281,12 +340,15 @@ def run_job(a, torch, dist, dev, rank, world, W, H, label, with_cpu):
         e.begin()
     total = enc.advance(0)
     per_picture = total // F
-    P = F if a.pictures <= 0 else min(F, a.pictures)
     SAMPLE_STEPS = 2
-    run_steps = P * per_picture
     n = a.warmup + a.steps
-    per = max(1, run_steps // n)
-    sizes = [per] * (n - 1) + [max(0, run_steps - per * (n - 1))]
+    per = step_ctus(per_picture)
+    if n * per > total:
+        raise SystemExit("bench.py: --warmup + --steps = %d steps of %d lockstep CTU steps each run past the end of the %d-frame GOP at %dx%d (%d steps at most)"
+                         % (n, per, F, W, H, total // per))
+    sizes = [per] * n
+    run_steps = n * per
+    P = pictures_done(run_steps, per_picture)[0]  # the pictures the steps reach into (the last one may be left part way)
 
     L = lib.load()
     # which walk every batch's steps run (walk.hip: by the chains in lockstep, or pinned by --walk; presets slow and placebo: the fused walk at any width, xh_walk_only)
@@ -330,15 +392,17 @@ def run_job(a, torch, dist, dev, rank, world, W, H, label, with_cpu):
 
     run_slices(0, a.warmup)
     fence()
-    lib.prof_enable(None)
-    lib.prof_read()
-    fence()
+    if full:
+        lib.prof_enable(None)
+        lib.prof_read()
+        fence()
     t0 = time.perf_counter()
-    run_slices(a.warmup, n, timers=True)
+    run_slices(a.warmup, n, timers=full)
     fence()
     dt = time.perf_counter() - t0
-    drain()
-    lib.prof_enable(None)
+    if full:
+        drain()
+        lib.prof_enable(None)
     k_ms, k_n, k_units = live
     if cpu is not None:
         cpu.start()
@@ -354,8 +418,45 @@ def run_job(a, torch, dist, dev, rank, world, W, H, label, with_cpu):
     for s in range(first_timed, first_timed + timed_steps):
         k = s // per_picture
         mix[k] = mix.get(k, 0) + 1
+    done = run_steps
+
+    def run_on(upto):  # the job on, untimed, to the end of picture `upto`
+        nonlocal done
+        if upto * per_picture > done:
+            for e in encs:
+                e.advance(upto * per_picture - done)
+            fence()
+            done = upto * per_picture
+
+    if dump_dir:  # the picture the timed steps left part way is finished first, so that the dump holds all their work
+        run_on(P)
+        if rank == 0:
+            dump_outputs(dump_dir, encs, Gs, P)
+    if full:  # to the end of picture --pictures (0: the whole GOP) or of the picture the steps left part way, whichever is later
+        P = max(P, F if a.pictures <= 0 else min(F, a.pictures))
+        run_on(P)
     rec = None
     if rank == 0:
+        basic = {"value": round(world * frames_timed / dt, 4), "ms_per_step": round(1e3 * dt / a.steps, 3),
+                 "config": {
+                     "workload": "%s: %d + %d bench steps of %d lockstep CTU steps (the first %d of %d pictures) of %d batches of %s closed GOPs x %d frames per GPU, %dx%d Baseline "
+                                 "preset %s (xeveb_app --preset %s --closed-gop -I 8 -m %d semantics), i.i.d. uniform 8-bit 4:2:0 input resident in HBM, QP 32"
+                                 % (label, a.warmup, a.steps, per, P, F, B, "+".join(str(g) for g in Gs), F, W, H, a.preset, a.preset, T),
+                     "walk": ["fused (one k_walk launch per step)" if f else "composed (~7 000 / ~11 000 launches per I / B step, on two streams)" for f in fused],
+                     "walk_choice": "presets slow and placebo run on the fused walk at any width (rdo_dbk_switch, 4x4 inter CUs: xh_common.h xh_walk_only)" if a.preset in ("slow", "placebo") else
+                                    "pinned by --walk / XEVE_HIP_WALK" if os.environ.get("XEVE_HIP_WALK") in ("0", "1") else
+                                    "the library's choice (walk.hip: since round 6 the composed walk at every width -- with its side stream it finishes a step sooner than the fused kernel "
+                                    "even at 8 chains; profiles/r06_side_stream.md)",
+                     "batches_side_by_side": B, "gops_in_lockstep": Gs, "frames_per_gop": F, "pictures_run": P, "row_chains_per_picture": T,
+                     "chains_in_lockstep": [g * min(T, h_lcu) for g in Gs], "lockstep_steps_per_picture": per_picture, "ctu_steps_per_step": per, "lockstep_steps_timed": timed_steps,
+                     "timed_picture_mix": {"picture_%d%s" % (k, "_IDR" if k == 0 else "_B"): round(v / per_picture, 3) for k, v in sorted(mix.items())},
+                     "frames_in_timed_region": round(frames_timed, 2), "ctus_per_picture": w_lcu * h_lcu,
+                     "parallelism": "closed-GOP shards per GPU, no collectives" + (" [SELF-TEST: all ranks share GPU 0, gloo]" if os.environ.get("XEVE_BENCH_SHARE_GPU") == "1" else "")},
+                 "encode": {"host_seconds_issuing_steps": round(stats["step_seconds"], 3), "seconds_in_picture_ends": round(stats["picture_end_seconds"], 2),
+                            "note": "time the host spent inside the library's step calls (the fused walk is one launch per step) and inside the picture ends"}, "cpu": cpu}
+    if rank == 0 and not full:
+        rec = basic
+    elif rank == 0:
         gname, gold = golden_prefix(W, H, F, T, a.preset)
         for e in encs:
             e.flush()  # (the access unit of the last picture run: appended now instead of at the next picture's end, so that every picture that was run is checked)
@@ -411,24 +512,7 @@ def run_job(a, torch, dist, dev, rank, world, W, H, label, with_cpu):
                             "mfma_busy_over_all_simd_cycles": mf.get("mfma_busy_over_all_simd_cycles"), "avg_launch_s": mf.get("avg_launch_s"),
                             "mfma_i8_insts_per_launch": mf.get("mfma_i8_insts_per_launch"), "pmc_file": "profiles/" + msrc, "what": mf.get("what"),
                             "note": "a 32x32 / 64x64 transform is the only dense matrix product on the path; those blocks are < 1 % of a step's kernel time"}
-        rec = {"value": round(world * frames_timed / dt, 4), "ms_per_step": round(1e3 * dt / a.steps, 3),
-               "config": {
-                   "workload": "%s: the first %d of %d pictures of %d batches of %s closed GOPs x %d frames per GPU, %dx%d Baseline preset %s (xeveb_app --preset %s --closed-gop "
-                               "-I 8 -m %d semantics), i.i.d. uniform 8-bit 4:2:0 input resident in HBM, QP 32; %d lockstep CTU steps cut into %d + %d equal slices"
-                               % (label, P, F, B, "+".join(str(g) for g in Gs), F, W, H, a.preset, a.preset, T, run_steps, a.warmup, a.steps),
-                   "walk": ["fused (one k_walk launch per step)" if f else "composed (~7 000 / ~11 000 launches per I / B step, on two streams)" for f in fused],
-                   "walk_choice": "presets slow and placebo run on the fused walk at any width (rdo_dbk_switch, 4x4 inter CUs: xh_common.h xh_walk_only)" if a.preset in ("slow", "placebo") else
-                                  "pinned by --walk / XEVE_HIP_WALK" if os.environ.get("XEVE_HIP_WALK") in ("0", "1") else
-                                  "the library's choice (walk.hip: since round 6 the composed walk at every width -- with its side stream it finishes a step sooner than the fused kernel "
-                                  "even at 8 chains; profiles/r06_side_stream.md)",
-                   "batches_side_by_side": B, "gops_in_lockstep": Gs, "frames_per_gop": F, "pictures_run": P, "row_chains_per_picture": T,
-                   "chains_in_lockstep": [g * min(T, h_lcu) for g in Gs], "lockstep_steps_per_picture": per_picture, "lockstep_steps_timed": timed_steps,
-                   "timed_picture_mix": {"picture_%d%s" % (k, "_IDR" if k == 0 else "_B"): round(v / per_picture, 3) for k, v in sorted(mix.items())},
-                   "frames_in_timed_region": round(frames_timed, 2), "ctus_per_picture": w_lcu * h_lcu,
-                   "parallelism": "closed-GOP shards per GPU, no collectives" + (" [SELF-TEST: all ranks share GPU 0, gloo]" if os.environ.get("XEVE_BENCH_SHARE_GPU") == "1" else "")},
-               "encode": {"host_seconds_issuing_steps": round(stats["step_seconds"], 3), "seconds_in_picture_ends": round(stats["picture_end_seconds"], 2),
-                          "note": "time the host spent inside the library's step calls (the fused walk is one launch per step) and inside the picture ends"},
-               "bitstream_check": check, "roofline": roof, "cpu": cpu}
+        rec = dict(basic, bitstream_check=check, roofline=roof)
     for e in encs:  # (the job's HBM goes back; an unfinished run is abandoned)
         e.close()
     return rec, (cfg, Gs, per_picture, fb, cls)
@@ -571,7 +655,8 @@ def main():
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--gops", type=int, default=0, help="closed GOPs in lockstep per batch (0: as many as a batch holds at this picture size)")
     ap.add_argument("--frames", type=int, default=8, help="frames per GOP (8: the full -I 8 closed GOP, 1 IDR + 7 B pictures)")
-    ap.add_argument("--pictures", type=int, default=3, help="coded pictures of every GOP the bounded job runs (0: the whole job)")
+    ap.add_argument("--pictures", type=int, default=3, help="--full: after the timed steps the job runs on, untimed, to the end of this picture of every GOP (0: the whole GOP) "
+                    "and GOP 0 is checked against the reference's golden prefix")
     ap.add_argument("--threads", type=int, default=8, help="row chains per picture = the reference's -m")
     ap.add_argument("--batches", type=int, default=3, help="batches encoded side by side on this GPU (a host thread and a HIP stream each)")
     ap.add_argument("--walk", default=os.environ.get("XEVE_BENCH_WALK", "auto"), choices=["auto", "fused", "composed"],
@@ -584,6 +669,10 @@ def main():
     ap.add_argument("--no-width-sweep", action="store_true", help="skip the untimed extra that runs 1, 8 and 64 GOPs in lockstep (what the headline depends on; ~40 s)")
     ap.add_argument("--no-1080p", action="store_true", help="skip the same bounded job at 1920x1080 that follows the headline (north_star names both sizes; ~2 more minutes, after the timed region)")
     ap.add_argument("--with-1080p", action="store_true", help="(the default since round 5; kept so that older command lines still parse)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: the roofline's timers in the timed region, the bitstream check, the per-class / per-stage "
+                    "profile, the width sweep, the job at 1920x1080 and the CPU baseline (each --no-* option above still drops its part)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, finish the picture they left part way (untimed) and write what they "
+                    "produced (the GOPs' bitstreams: sizes, sums, a seeded sample; the pictures they hold) as DIR/*.npy")
     a = ap.parse_args()
     if a.walk == "composed":
         os.environ["XEVE_HIP_WALK"] = "0"
@@ -625,7 +714,8 @@ def main():
 
     xeve_amd.init(local)
     solo = rank == 0 and world == 1
-    rec, (cfg, Gs, per_picture, fb, cls) = run_job(a, torch, dist, dev, rank, world, a.width, a.height, "headline", solo and not a.no_cpu_baseline)
+    rec, (cfg, Gs, per_picture, fb, cls) = run_job(a, torch, dist, dev, rank, world, a.width, a.height, "headline", a.full and solo and not a.no_cpu_baseline,
+                                                   a.full, a.dump_outputs)
     line = None
     if rank == 0:
         cpu = rec.pop("cpu")
@@ -634,9 +724,11 @@ def main():
                 "dtype": "s16 samples, s32/s64 accumulation, f64 cost comparisons (bit-exact)", "data": "synthetic",
                 "value_is": "encoded frames/s of the closed-GOP batch encoder on full 8-frame closed GOPs: a real encode to EVC bitstreams (every stage of the reference's xeve_pic "
                             "on the device, NAL assembly on the host), byte-identical to the reference encoder; frames = the timed share of the pictures that were run",
-                "config": rec["config"], "encode": rec["encode"], "bitstream_check": rec["bitstream_check"], "roofline": rec["roofline"]}
+                "config": rec["config"], "encode": rec["encode"]}
+        if a.full:
+            line.update(bitstream_check=rec["bitstream_check"], roofline=rec["roofline"])
         line["config"]["library_built_in_this_run"] = built_here
-    if solo and not a.no_secondary:
+    if a.full and solo and not a.no_secondary:
         try:
             line["roofline"]["by_time"] = (stage_profile if cls == "walk" else class_profile)(torch, dev, cfg, max(8, Gs[0] // 4) if cls == "walk" else max(136, Gs[0] // 2), a.frames, per_picture, fb)
         except Exception as e:  # noqa: BLE001

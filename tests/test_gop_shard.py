@@ -160,16 +160,21 @@ def test_bench_with_two_ranks_sharing_the_gpu():
     port = s.getsockname()[1]
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--width", "256", "--height", "128", "--gops", "6", "--frames", "8", "--pictures", "3",
-           "--batches", "2", "--no-cpu-baseline"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "4", "--width", "256", "--height", "128", "--gops", "6", "--frames", "8", "--pictures", "3",
+           "--batches", "2", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=dict(os.environ, XEVE_BENCH_SHARE_GPU="1", PYTHONPATH=ROOT, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]  # rank 0 alone speaks
     r = json.loads(lines[0])
-    assert r["n_gpus"] == 2 and r["steps"] == 3 and r["warmup"] == 1 and r["scaling"] == "weak" and r["value"] > 0
+    assert r["n_gpus"] == 2 and r["steps"] == 12 and r["warmup"] == 4 and r["scaling"] == "weak" and r["value"] > 0
     assert r["config"]["gops_in_lockstep"] == [6, 6] and r["config"]["pictures_run"] == 3
     assert r["bitstream_check"]["all_seeded_gops_same_bytes"] and r["bitstream_check"]["gop0_bytes_so_far"] > 0
-    # both ranks' frames are in the aggregate: 2 ranks x 12 GOPs x the timed share (3 of 4 slices of 3 pictures)
-    assert abs(r["config"]["frames_in_timed_region"] - 12 * 3 * 0.75) < 4.0
+    # a rank's 12 GOPs x the timed share of a picture (12 timed steps of a fixed number of lockstep CTU steps each; `value` counts both ranks' frames)
+    c = r["config"]
+    import bench
+
+    assert c["ctu_steps_per_step"] == bench.step_ctus(c["lockstep_steps_per_picture"]) and c["lockstep_steps_timed"] == 12 * c["ctu_steps_per_step"]
+    assert c["pictures_run"] == max(3, bench.pictures_done(16 * c["ctu_steps_per_step"], c["lockstep_steps_per_picture"])[0])
+    assert abs(c["frames_in_timed_region"] - 12 * c["lockstep_steps_timed"] / c["lockstep_steps_per_picture"]) < 0.01
     assert r["roofline"]["launches_in_region"] > 0
