@@ -210,22 +210,6 @@ def test_hip_ctu_rows_of_a_b_picture_as_chains_of_one_call():
     assert np.array_equal(mod[0].cpu().numpy(), c["mod"][0]) and np.array_equal(mv.cpu().numpy(), m["mv"]) and np.array_equal(ms.cpu().numpy().view(np.uint32), m["scu"])
 
 
-def test_hip_ctu_mode_decision_with_the_lane_serial_node_kernel(tmp_path, each_walk):
-    """XEVE_HIP_TREE_LANE=1 (off by default: measured slower): the 4x4 / 8x8 nodes of the COMPOSED walk decided by one lane per chain (csrc/cu_lane.h).  The
-    switch is read once per process, so a fresh interpreter runs three of the cases above with it on (composed walk pinned); the same comparison against the oracle must hold."""
-    import os
-    import subprocess
-    import sys
-
-    if each_walk != "composed":
-        pytest.skip("the lane-serial node kernel belongs to the composed walk: run once, with it pinned")
-    env = dict(os.environ, XEVE_HIP_TREE_LANE="1")
-    here = os.path.dirname(os.path.abspath(__file__))
-    p = subprocess.run([sys.executable, "-m", "pytest", os.path.join(here, "test_hip_tree.py"), "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", "-k",
-                        "matches_oracle and composed and (3101 or 3104 or 4103)"], env=env, capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0 and "9 passed" in p.stdout, p.stdout[-1500:] + p.stderr[-500:]  # (three cases x {side stream, one stream, a side stream per level})
-
-
 def test_hip_ctu_host_form_over_two_b_pictures():
     """xeve_hip_mode_analyze_ctu_host (what ctx->fn_mode_analyze_lcu is pointed at) called directly, CTU by CTU, over TWO B pictures of one size one after the other:
     host planes and maps, resident pictures announced per picture, the per-thread device buffers reused -- what the first picture left in them (every unit coded)

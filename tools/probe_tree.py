@@ -1,7 +1,7 @@
 """Time of one CTU step of the device-side I-picture tree walk (xeve_hip_mode_analyze_ctu_jobs) against the number of chains in lockstep (xeve_amd/workload.py
 CtuWalkIntra: every chain is a 128x128 picture of its own; a step decides the same CTU of every picture).
-usage: [XEVE_HIP_TREE_GRAPH=1] python tools/probe_tree.py [--chains=1,64,256,1024] [--content=noise|smooth|texture] [--write]
-(with the graph switch on, steps 5 .. 7 are replays and steps 2 .. 3 launch-by-launch; off, all are launch-by-launch)"""
+usage: python tools/probe_tree.py [--chains=1,64,256,1024] [--content=noise|smooth|texture] [--write]
+(every step is launch-by-launch; steps 5 .. 7 and 2 .. 3 are reported apart: the first steps carry the library's warm-up)"""
 import os
 import sys
 import time

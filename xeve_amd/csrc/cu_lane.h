@@ -5,8 +5,9 @@
 // work); decided by one lane it is one launch for all chains, and the parallel axis is the only one the problem has: the chains (64 per wave).  The code is
 // therefore plain scalar C++ per lane -- neighbours, the five predictors, SATD, the candidate list, per candidate the residual, DCT, RDOQ, the intra luma syntax
 // through the arithmetic coder, reconstruction and SSD; chroma with the winner's mode; the CU's cost from the whole syntax and the exit coder state.
-// Every function is __host__ __device__: libxeve_hip.so instantiates the device side only (k_intra_lane in tree.hip); tests/native builds the same functions for
-// the host so that `pytest -m "not gpu"` checks them bit for bit against the oracle without a GPU.
+// Every function is __host__ __device__: tests/native builds them for the host so that `pytest -m "not gpu"` checks them bit for bit against the oracle without a
+// GPU.  The analysis half (intra_cu and what only it calls) has no GPU caller any more -- its kernel in tree.hip measured slower than the batched composite
+// (profiles/r02_tree_lane.log) and was removed; libxeve_hip.so instantiates the coder and the syntax writer, through eco_lane.h.
 #pragma once
 #include <stdint.h>
 #include "../../include/xeve_hip.h"

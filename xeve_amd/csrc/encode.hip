@@ -123,16 +123,16 @@ __device__ __forceinline__ void sbac_out(xeve_hip_sbac *__restrict__ g, xl::Sbac
 }
 // the writer of the first pass: chain c writes the CTU it has just decided on its own coder; the bytes are kept only where they are the slice data (one chain per
 // picture: cap > 0), appended at pos[g]
-template <bool WAVE> __global__ void __launch_bounds__(64) k_enc_write(const xeve_hip_ctu_data *__restrict__ ctus, xeve_hip_sbac *__restrict__ states, xl::EcoParams E, uint32_t *map_scu,
+__global__ void __launch_bounds__(64) k_enc_write(const xeve_hip_ctu_data *__restrict__ ctus, xeve_hip_sbac *__restrict__ states, xl::EcoParams E, uint32_t *map_scu,
                                                   const int8_t *map_ipm, const uint8_t *map_tidx, uint32_t *map_cu_mode, long map_pic,
                                                   const xeve_hip_ctu_job *__restrict__ jobs, int nchains, uint8_t *__restrict__ bytes, long cap, int32_t *__restrict__ pos)
 {
-    // ONE CHAIN PER WAVE, one lane working: an arithmetic coder's control flow follows its data bin by bin, so chains packed into the lanes of a wave run one after
+    // ONE CHAIN PER WAVE: an arithmetic coder's control flow follows its data bin by bin, so chains packed into the lanes of a wave run one after
     // the other (measured: 16 chains per wave, 78 ms per CTU of noise; a lone chain, 13 ms) -- a wave per chain keeps every chain at the speed of a lone one, and the
-    // chip holds a thousand waves.  WAVE: the 64 lanes run the chain's writer in step (identical state, bins and bytes) and share the scan of the coefficient
-    // blocks (eco_lane.h eco_levels); without it lane 0 works alone
+    // chip holds a thousand waves.  The 64 lanes run the chain's writer in step (identical state, bins and bytes) and share the scan of the coefficient
+    // blocks (eco_lane.h eco_levels)
     const int c = blockIdx.x;
-    if(c >= nchains || (!WAVE && threadIdx.x != 0)) return;
+    if(c >= nchains) return;
     const xeve_hip_ctu_job J = jobs[c];
     xl::Sbac s;
     sbac_in(s, states + J.sbac);
@@ -143,24 +143,24 @@ template <bool WAVE> __global__ void __launch_bounds__(64) k_enc_write(const xev
     if(!cap) s.code_bits = 0x3FFFFFFFu;
     const int at = cap ? pos[J.pic] : 0;
     xl::Sink o = {cap ? bytes + (long)J.pic * cap + at : nullptr, cap ? (int)(cap - at) : 0, 0};
-    xl::eco_ctu<WAVE>(E, s, ctus[c], map_scu + J.pic * map_pic, map_ipm + J.pic * map_pic, map_tidx + J.pic * map_pic, map_cu_mode + J.pic * map_pic, J.x, J.y, &o);
+    xl::eco_ctu<true>(E, s, ctus[c], map_scu + J.pic * map_pic, map_ipm + J.pic * map_pic, map_tidx + J.pic * map_pic, map_cu_mode + J.pic * map_pic, J.x, J.y, &o);
     if(!cap) s.code = 0, s.code_bits = 11, s.stacked_ff = s.stacked_zero = s.pending_byte = s.is_pending_byte = 0, s.bitcounter = 0;
     sbac_out(states + J.sbac, s);
     if(cap) pos[J.pic] = at + o.n;
 }
 // the second pass (xeve_enc.c:466-560): GOP g's CTUs [lcu0, lcu1) in raster order on the picture's own coder
-template <bool WAVE> __global__ void __launch_bounds__(64) k_enc_rewrite(const xl::CtuSyntax *__restrict__ store, xeve_hip_sbac *__restrict__ states, xl::EcoParams E, uint32_t *map_scu,
+__global__ void __launch_bounds__(64) k_enc_rewrite(const xl::CtuSyntax *__restrict__ store, xeve_hip_sbac *__restrict__ states, xl::EcoParams E, uint32_t *map_scu,
                                                     const int8_t *map_ipm, const uint8_t *map_tidx, uint32_t *map_cu_mode, long map_pic, int G, int f_lcu, int w_lcu,
                                                     int lcu0, int lcu1, uint8_t *__restrict__ bytes, long cap, int32_t *__restrict__ pos)
 {
-    const int g = blockIdx.x; // (one GOP per wave, one lane working: see k_enc_write)
-    if(g >= G || (!WAVE && threadIdx.x != 0)) return;
+    const int g = blockIdx.x; // (one GOP per wave: see k_enc_write)
+    if(g >= G) return;
     xl::Sbac s;
     sbac_in(s, states + g);
     int at = pos[g];
     for(int lcu = lcu0; lcu < lcu1; lcu++) {
         xl::Sink o = {bytes + (long)g * cap + at, (int)(cap - at), 0};
-        xl::eco_ctu<WAVE>(E, s, store[(long)g * f_lcu + lcu], map_scu + g * map_pic, map_ipm + g * map_pic, map_tidx + g * map_pic, map_cu_mode + g * map_pic, (lcu % w_lcu) * CTU,
+        xl::eco_ctu<true>(E, s, store[(long)g * f_lcu + lcu], map_scu + g * map_pic, map_ipm + g * map_pic, map_tidx + g * map_pic, map_cu_mode + g * map_pic, (lcu % w_lcu) * CTU,
                     (lcu / w_lcu) * CTU, &o);
         at += o.n;
     }
@@ -429,12 +429,6 @@ struct xeve_hip_enc {
         if(error.empty()) k_enc_reset_chain<<<(G + 63) / 64, 64, 0, st>>>(states.as<xeve_hip_sbac>(), T, t, G);
     }
     bool keeps_store() const { return store2[0].p != nullptr; }
-    // the writer kernels on whole waves (eco_lane.h eco_levels) unless XEVE_HIP_WRITER_WAVE=0 (developer switch: the lone-lane form, for comparison)
-    static bool writer_wave()
-    {
-        static const bool v = !getenv("XEVE_HIP_WRITER_WAVE") || atoi(getenv("XEVE_HIP_WRITER_WAVE")) != 0;
-        return v;
-    }
     xl::CtuSyntax *store_now() const { return store2[cur_store].as<xl::CtuSyntax>(); }
     void step(const ChainCtu *c, int n)
     {
@@ -463,12 +457,8 @@ struct xeve_hip_enc {
                   "xeve_hip_mode_analyze_ctu_jobs"))
             return;
         if(keeps_store()) k_enc_keep<<<dim3(4, nch), 256, 0, st>>>(out.as<xeve_hip_ctu_data>(), store_now(), D, G, f_lcu);
-        if(writer_wave())
-            k_enc_write<true><<<nch, 64, 0, st>>>(out.as<xeve_hip_ctu_data>(), states.as<xeve_hip_sbac>(), E, scu.as<uint32_t>(), ipm.as<int8_t>(), tidx.as<uint8_t>(), cum.as<uint32_t>(),
-                                                  map_pic, jobs.as<xeve_hip_ctu_job>(), nch, slice.as<uint8_t>(), rewrite_mode ? 0 : slice_cap, pos.as<int32_t>());
-        else
-            k_enc_write<false><<<nch, 64, 0, st>>>(out.as<xeve_hip_ctu_data>(), states.as<xeve_hip_sbac>(), E, scu.as<uint32_t>(), ipm.as<int8_t>(), tidx.as<uint8_t>(), cum.as<uint32_t>(),
-                                                   map_pic, jobs.as<xeve_hip_ctu_job>(), nch, slice.as<uint8_t>(), rewrite_mode ? 0 : slice_cap, pos.as<int32_t>());
+        k_enc_write<<<nch, 64, 0, st>>>(out.as<xeve_hip_ctu_data>(), states.as<xeve_hip_sbac>(), E, scu.as<uint32_t>(), ipm.as<int8_t>(), tidx.as<uint8_t>(), cum.as<uint32_t>(), map_pic,
+                                        jobs.as<xeve_hip_ctu_job>(), nch, slice.as<uint8_t>(), rewrite_mode ? 0 : slice_cap, pos.as<int32_t>());
         hip_ok(hipGetLastError(), "step kernels");
         n_steps++, t_steps += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
@@ -501,14 +491,9 @@ struct xeve_hip_enc {
             fin = rw_states.as<xeve_hip_sbac>(), fin_stride = 1;
             k_enc_reset_chain<<<(G + 63) / 64, 64, 0, st2>>>(fin, 1, 0, G);
             xl::EcoParams Ew = E; // (the pass's own copy: E follows the next picture)
-            for(int row = 0; row < h_lcu; row++) {
-                if(writer_wave())
-                    k_enc_rewrite<true><<<G, 64, 0, st2>>>(store_now(), fin, Ew, rw_scu.as<uint32_t>(), rw_ipm.as<int8_t>(), tidx.as<uint8_t>(), rw_cum.as<uint32_t>(), map_pic, G,
-                                                           f_lcu, w_lcu, row * w_lcu, (row + 1) * w_lcu, slice.as<uint8_t>(), slice_cap, pos.as<int32_t>());
-                else
-                    k_enc_rewrite<false><<<G, 64, 0, st2>>>(store_now(), fin, Ew, rw_scu.as<uint32_t>(), rw_ipm.as<int8_t>(), tidx.as<uint8_t>(), rw_cum.as<uint32_t>(), map_pic, G,
-                                                            f_lcu, w_lcu, row * w_lcu, (row + 1) * w_lcu, slice.as<uint8_t>(), slice_cap, pos.as<int32_t>());
-            }
+            for(int row = 0; row < h_lcu; row++)
+                k_enc_rewrite<<<G, 64, 0, st2>>>(store_now(), fin, Ew, rw_scu.as<uint32_t>(), rw_ipm.as<int8_t>(), tidx.as<uint8_t>(), rw_cum.as<uint32_t>(), map_pic, G, f_lcu, w_lcu,
+                                                 row * w_lcu, (row + 1) * w_lcu, slice.as<uint8_t>(), slice_cap, pos.as<int32_t>());
             rows_pending = true;
             if(two_stores) cur_store ^= 1;
         }

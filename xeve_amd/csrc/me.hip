@@ -3,33 +3,17 @@
 // reference: me_ipel_diamond  src_base/xeve_pinter.c:363-551, with get_mv_bits (:74-120), MV_COST (:47) and the
 // re-centring of get_range_ipel (:122-140).  ONE WAVE PER JOB runs the whole data-dependent search: round 0 is the
 // dense (2d+1)^2 grid around the clipped start, later rounds are 4 / 8 / 16-point diamonds of doubling radius around
-// the INITIAL centre, until `faststep` rounds pass without improvement.  Per candidate the block SAD is a DPP
-// butterfly over the candidate's lane group (same lane layout as k_sad_sq); per round the winner is a wave-wide
-// minimum over 64-bit keys (cost << 32 | evaluation order), which reproduces the reference's
-// "first strictly smaller cost wins" tie-break exactly.
-#include <cstdlib>
+// the INITIAL centre, until `faststep` rounds pass without improvement.
+//
+// ONE CANDIDATE PER LANE.  A lane owns a candidate: it walks the block's rows itself (reference row segment from the plane, original row segment broadcast
+// from a per-wave LDS copy), so a SAD needs no cross-lane reduction, the vector cost is computed once per candidate, and a round's winner is one 32-bit wave
+// minimum plus a ballot (lanes are in evaluation order, so the lowest lane among the minima is the reference's "first strictly smaller cost wins").  The dense
+// (2d+1)^2 round is one pass (two for the 121 candidates of the bi-prediction refinement); the rings that are certain to be evaluated -- the search only stops
+// after `faststep` rounds without improvement -- share one pass as well, and the bookkeeping then consumes their minima ring by ring, in the reference's order.
+// (An earlier mapping spread a block over the lanes and paid a cross-lane sum and a 64-bit cross-group minimum for every 1 .. 8 candidates; it was bound by that
+// bookkeeping -- profiles/r02_search_pmc.json, profiles/r02_lds_search.md -- and is gone; see the history.)
 #include <hip/hip_ext.h>
 #include "xh_common.h"
-
-// developer switch (measurement): 0 = every candidate row through the vector L1 (default: measured fastest), 1 = dense round from an LDS window
-static const int g_me_lds = getenv("XEVE_HIP_ME_LDS") ? atoi(getenv("XEVE_HIP_ME_LDS")) : 0;
-// developer switch (measurement): 1 = one candidate per lane (cpl_*), 0 = the block spread over the lanes (me_*)
-static const int g_me_cpl = getenv("XEVE_HIP_ME_CPL") ? atoi(getenv("XEVE_HIP_ME_CPL")) : 1;
-
-template <int S> struct MGeo {
-    static constexpr int LPR = S / 8, RPP = XH_WAVE / LPR, CPP = RPP >= S ? RPP / S : 1, NP = RPP >= S ? 1 : S / RPP, GROUP = XH_WAVE / CPP;
-};
-
-// The dense round's window in LDS (LDSM != 0): every candidate of the (2d+1)^2 grid reads its rows out of ONE staged copy of the
-// (S + 2d) x (S + 2d) samples the grid covers -- staged with coalesced dword loads (a row of the window is contiguous in the plane),
-// read back as 16-byte row segments at any 2-byte offset (unaligned ds_read_b128).  d = 2 (uni) / 5 (bi-prediction refinement),
-// xeve_pinter.c:409-416.  One window per wave.  MEASURED (profiles/r02_lds_search.md): on one MI355X the window does not pay -- the search class of a
-// 3840x2160 picture takes 16.4 ms through the vector L1, 17.3 ms with the window, 18.4 ms with a second, dword-aligned copy of it (two ds_read2_b32 per
-// segment; since removed) -- so the L1 path stays the default and this form is kept behind XEVE_HIP_ME_LDS=1 for reproduction.
-template <int S, bool BI> struct MWin {
-    static constexpr int DMAX = BI ? 5 : 2, H = S + 2 * DMAX, NDW = S / 2 + DMAX + 1, PITCH = 2 * NDW; // NDW dwords = S + 2 DMAX + 2 samples: + parity, + round-up
-    static constexpr int PELS = H * PITCH;
-};
 
 // 16-point diamond of L1 radius 4 (xeve_pinter.c:57-65); the 8-point ring is every other point halved
 __device__ __constant__ int8_t c_dia16[16][2] = {{-4, 0}, {-3, 1}, {-2, 2}, {-1, 3}, {0, 4}, {1, 3}, {2, 2}, {3, 1},
@@ -43,246 +27,6 @@ __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlan
 template <int CTRL, int ROWS> __device__ __forceinline__ int dpp_rows(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, ROWS, 0xf, false); } // (rows not named keep v)
 #define XH_DPP_ROW_BCAST15 0x142 // lane 15 of a row -> every lane of the next row
 #define XH_DPP_ROW_BCAST31 0x143 // lane 31 -> every lane of rows 2 and 3
-// the minimum of a 64-bit key over the wave and the payload of the lane that holds it; both wave-uniform on return (keys are distinct, or ~0 with no payload of interest)
-__device__ __forceinline__ void wave_min_key(unsigned long long &key, int &pay)
-{
-#define XH_KEY_STEP(EX)                                                                      \
-    {                                                                                        \
-        const unsigned lo = (unsigned)EX((int)(unsigned)key), hi = (unsigned)EX((int)(unsigned)(key >> 32)); \
-        const int      ob = EX(pay);                                                         \
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;                   \
-        if(o < key) key = o, pay = ob;                                                       \
-    }
-    XH_KEY_STEP(xh_dpp<XH_DPP_QUAD_XOR1>)
-    XH_KEY_STEP(xh_dpp<XH_DPP_QUAD_XOR2>)
-    XH_KEY_STEP(xh_dpp<XH_DPP_ROW_HALF_MIRROR>)
-    XH_KEY_STEP(xh_dpp<XH_DPP_ROW_MIRROR>)
-    XH_KEY_STEP((dpp_rows<XH_DPP_ROW_BCAST15, 0xA>))
-    XH_KEY_STEP((dpp_rows<XH_DPP_ROW_BCAST31, 0xC>))
-#undef XH_KEY_STEP
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)key, 63), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(key >> 32), 63);
-    key = ((unsigned long long)hi << 32) | lo, pay = __builtin_amdgcn_readlane(pay, 63);
-}
-
-// the original block of a job (org_bi for bi-prediction refinement: 2*org - pred, may be negative): loaded once, kept in registers
-template <int S, bool BI>
-__device__ __forceinline__ void me_load_org(const pel *__restrict__ org0, int s_org, const pel *__restrict__ org_bi, int x, int y, int org_off, int lane,
-                                            u32x4 (&org)[MGeo<S>::NP])
-{
-    using G = MGeo<S>;
-    const int gl = lane % G::GROUP, row0 = gl / G::LPR, col = (gl % G::LPR) * 8;
-    const pel *o  = BI ? org_bi + org_off : org0 + (long)y * s_org + x;
-    const int  so = BI ? S : s_org;
-#pragma unroll
-    for(int p = 0; p < G::NP; p++) {
-        org[p] = xh_ld8(o + (row0 + p * G::RPP) * so + col);
-        if(BI) org[p] ^= 0x80008000u; // bias once: v_sad_u16 is unsigned
-    }
-}
-
-// one complete me_ipel_diamond by the calling wave; the result is wave-uniform
-template <int S, bool BI, int LDSM = 0>
-__device__ __forceinline__ xeve_hip_me_result me_diamond(const u32x4 (&org)[MGeo<S>::NP], const pel *__restrict__ ref0, int s_ref, const xeve_hip_me_job &jb, int shift,
-                                                         const xeve_hip_me_params &P, int lane, int *range_out = nullptr, unsigned *evals = nullptr,
-                                                         pel *win = nullptr)
-{
-    using W = MWin<S, BI>;
-    using G = MGeo<S>;
-    const int slot = lane / G::GROUP, gl = lane % G::GROUP, row0 = gl / G::LPR, col = (gl % G::LPR) * 8;
-    unsigned nev = 0; // block SADs evaluated (measurement only: xeve_hip_prof_*)
-    int r0 = jb.range[0], r1 = jb.range[1], r2 = jb.range[2], r3 = jb.range[3];
-    int bx = clip3(P.min_clip[0], P.max_clip[0], jb.mvi[0] >> 2), by = clip3(P.min_clip[1], P.max_clip[1], jb.mvi[1] >> 2);
-    const int ix = bx, iy = by;
-    unsigned long long best_key = 0xFFFFFFFF00000000ull; // cost_best = UINT32_MAX, order 0 (nothing evaluated beats it on a tie)
-    int best_bits = 0, beststep = jb.beststep_in, step = 0, not_found = 0;
-    unsigned order = 1;
-    const int d = P.bi == 1 ? 5 : 2; // BI_STEP : 2 (xeve_pinter.c:409-416)
-
-    for(;;) {
-        not_found++;
-        // ---- candidate set of this round
-        const bool dense = step <= 2, coarse = step > 8;
-        int x0 = 0, y0 = 0, wd = 1, nc;
-        if(dense) {
-            x0 = bx <= r0 ? bx : bx - d, y0 = by <= r1 ? by : by - d;
-            const int x1 = bx >= r2 ? bx : bx + d, y1 = by >= r3 ? by : by + d;
-            wd = x1 - x0 + 1;
-            nc = wd * (y1 - y0 + 1);
-        }
-        else nc = coarse ? 16 : (step == 4 ? 5 : 9);
-        unsigned long long round_key = ~0ull;
-        int round_bits = 0;
-        // ---- the dense grid out of the LDS window
-        bool staged = false;
-        int  wpar = 0;
-        if(LDSM && dense && !(s_ref & 1) && wd <= 2 * W::DMAX + 1 && nc <= (2 * W::DMAX + 1) * wd) {
-            const pel      *g0   = ref0 + (long)y0 * s_ref + x0;
-            wpar                 = (int)(((uintptr_t)g0 >> 1) & 1);
-            const uint32_t *ga   = reinterpret_cast<const uint32_t *>(g0 - wpar); // dword-aligned; row r starts s_ref / 2 dwords further
-            const int       nrow = nc / wd + S - 1, tot = nrow * W::NDW, sdw = s_ref >> 1;
-            uint32_t       *wa   = reinterpret_cast<uint32_t *>(win);
-            for(int i = lane; i < tot; i += 64) {
-                const int r = i / W::NDW, k = i - r * W::NDW;
-                const uint32_t *gp = ga + (long)r * sdw + k;
-                wa[i] = gp[0];
-            }
-            __builtin_amdgcn_wave_barrier(); // (LDS operations of one wave execute in order; this only pins the compiler's schedule)
-            staged = true;
-        }
-        for(int c0 = 0; c0 < nc; c0 += G::CPP) {
-            const int k = c0 + slot;
-            int mx, my;
-            if(dense) {
-                const int q = k / wd;
-                mx = x0 + (k - q * wd), my = y0 + q;
-            }
-            else if(coarse) mx = ix + (step >> 2) * c_dia16[k & 15][0], my = iy + (step >> 2) * c_dia16[k & 15][1];
-            else {
-                const int i = step == 4 ? 2 * k : k; // 4-point ring skips the odd points; i == 8 is the centre
-                const int dx = i < 8 ? c_dia16[(2 * i) & 15][0] / 2 : 0, dy = i < 8 ? c_dia16[(2 * i) & 15][1] / 2 : 0;
-                mx = ix + (step >> 1) * dx, my = iy + (step >> 1) * dy;
-            }
-            const bool valid = k < nc && mx <= r2 && mx >= r0 && my <= r3 && my >= r1;
-            if(evals) nev += (unsigned)__popcll(__ballot(valid && gl == 0));
-            int acc = 0;
-            if(LDSM && staged) {
-                if(valid) {
-                    const int wx = mx - x0 + wpar + col; // sample offset inside a window row
-                    // (explicit LDS address space: with a generic pointer the compiler folds this load and the global one below into one flat load)
-                    typedef __attribute__((address_space(3))) const pel lds_pel;
-                    lds_pel *r = (lds_pel *)win + (my - y0 + row0) * W::PITCH + wx;
-#pragma unroll
-                    for(int p = 0; p < G::NP; p++) {
-                        u32x4 v = *(__attribute__((address_space(3))) const u32x4_a2 *)(r + p * G::RPP * W::PITCH);
-                        if(BI) v ^= 0x80008000u;
-                        acc = __builtin_amdgcn_sad_u16(org[p].x, v.x, acc);
-                        acc = __builtin_amdgcn_sad_u16(org[p].y, v.y, acc);
-                        acc = __builtin_amdgcn_sad_u16(org[p].z, v.z, acc);
-                        acc = __builtin_amdgcn_sad_u16(org[p].w, v.w, acc);
-                    }
-                }
-            }
-            else if(valid) {
-                const pel *r = ref0 + (long)(my + row0) * s_ref + mx + col;
-#pragma unroll
-                for(int p = 0; p < G::NP; p++) {
-                    u32x4 v = xh_ld8(r + (long)p * G::RPP * s_ref);
-                    if(BI) v ^= 0x80008000u;
-                    acc = __builtin_amdgcn_sad_u16(org[p].x, v.x, acc);
-                    acc = __builtin_amdgcn_sad_u16(org[p].y, v.y, acc);
-                    acc = __builtin_amdgcn_sad_u16(org[p].z, v.z, acc);
-                    acc = __builtin_amdgcn_sad_u16(org[p].w, v.w, acc);
-                }
-            }
-            acc = xh_group_sum<G::GROUP>(acc);
-            int bits = xh_mvd_bits((mx << 2) - jb.gmvp[0]) + xh_mvd_bits((my << 2) - jb.gmvp[1]) + P.refi_bits;
-            if(BI) bits += P.extra_bits;
-            const int sad = acc >> shift;
-            const unsigned cost = ((P.lambda_mv * (unsigned)bits + (1u << 15)) >> 16) + (unsigned)(BI ? sad >> 1 : sad);
-            unsigned long long key = valid ? ((unsigned long long)cost << 32) | (order + (unsigned)k) : ~0ull;
-            int kb = bits;
-            // minimum over the CPP candidate groups of this pass (every lane of a group holds the same key)
-            wave_min_key(key, kb);
-            if(key < round_key) round_key = key, round_bits = kb;
-        }
-        // ---- wave-uniform bookkeeping (everything below is identical in all lanes; force it into SGPRs)
-        const unsigned rk_hi = (unsigned)uni((int)(round_key >> 32)), rk_lo = (unsigned)uni((int)round_key);
-        round_key  = ((unsigned long long)rk_hi << 32) | rk_lo;
-        round_bits = uni(round_bits);
-        if(round_key < best_key) { // cost < cost_best, earliest candidate on ties
-            best_key = round_key, best_bits = round_bits, not_found = 0;
-            const int k = (int)(rk_lo - order);
-            if(dense) {
-                const int q = k / wd;
-                bx = x0 + (k - q * wd), by = y0 + q, beststep = 2;
-            }
-            else {
-                int dx, dy, mul;
-                if(coarse) dx = c_dia16[k][0], dy = c_dia16[k][1], mul = step >> 2;
-                else {
-                    const int i = step == 4 ? 2 * k : k;
-                    dx = i < 8 ? c_dia16[(2 * i) & 15][0] / 2 : 0, dy = i < 8 ? c_dia16[(2 * i) & 15][1] / 2 : 0, mul = step >> 1;
-                }
-                bx = ix + mul * dx, by = iy + mul * dy, beststep = step;
-            }
-            bx = uni(bx), by = uni(by);
-        }
-        order += (unsigned)nc;
-        if(dense) { // get_range_ipel around the best position so far (xeve_pinter.c:463-468, 122-140)
-            const int sr = P.bi == 1 ? 5 : P.range_recentre;
-            r0 = clip3(P.min_clip[0], P.max_clip[0], bx - sr), r2 = clip3(P.min_clip[0], P.max_clip[0], bx + sr);
-            r1 = clip3(P.min_clip[1], P.max_clip[1], by - sr), r3 = clip3(P.min_clip[1], P.max_clip[1], by + sr);
-            step += 2;
-        }
-        if(not_found == P.faststep) break;
-        if(P.bi == 1) break;
-        step <<= 1;
-        if(step > P.max_search_range) break;
-    }
-    xeve_hip_me_result res;
-    res.mv[0] = (int16_t)((bx - jb.x) << 2), res.mv[1] = (int16_t)((by - jb.y) << 2);
-    res.cost = (uint32_t)(best_key >> 32), res.beststep = beststep, res.best_mv_bits = best_bits;
-    if(range_out) range_out[0] = r0, range_out[1] = r1, range_out[2] = r2, range_out[3] = r3; // the caller's `range`, re-centred in place (:463-468)
-    if(evals) *evals += nev;
-    return res;
-}
-
-// A list of integer positions evaluated by the calling wave in the list's order: cost = MV_COST + SAD, a position wins only with a strictly
-// smaller cost than `cost_best`, the earliest on ties (me_raster, its 3x3 refinement grids, me_ipel_refinement).  gen(k, mx, my) -> valid.
-template <int S, bool BI, class Gen>
-__device__ __forceinline__ void me_eval(const u32x4 (&org)[MGeo<S>::NP], const pel *__restrict__ ref0, int s_ref, int nc, Gen gen, int gmvp_x, int gmvp_y, int shift,
-                                        const xeve_hip_me_params &P, int lane, unsigned &cost_best, int &best_bits, int &bx, int &by)
-{
-    using G = MGeo<S>;
-    const int slot = lane / G::GROUP, gl = lane % G::GROUP, row0 = gl / G::LPR, col = (gl % G::LPR) * 8;
-    unsigned long long best_key = (unsigned long long)cost_best << 32; // order 0: an equal cost never beats it
-    int win = -1, win_bits = 0;
-    for(int c0 = 0; c0 < nc; c0 += G::CPP) {
-        const int k = c0 + slot;
-        int mx = 0, my = 0;
-        const bool valid = k < nc && gen(k, mx, my);
-        int acc = 0;
-        if(valid) {
-            const pel *r = ref0 + (long)(my + row0) * s_ref + mx + col;
-#pragma unroll
-            for(int p = 0; p < G::NP; p++) {
-                u32x4 v = xh_ld8(r + (long)p * G::RPP * s_ref);
-                if(BI) v ^= 0x80008000u;
-                acc = __builtin_amdgcn_sad_u16(org[p].x, v.x, acc);
-                acc = __builtin_amdgcn_sad_u16(org[p].y, v.y, acc);
-                acc = __builtin_amdgcn_sad_u16(org[p].z, v.z, acc);
-                acc = __builtin_amdgcn_sad_u16(org[p].w, v.w, acc);
-            }
-        }
-        acc = xh_group_sum<G::GROUP>(acc);
-        int bits = xh_mvd_bits((mx << 2) - gmvp_x) + xh_mvd_bits((my << 2) - gmvp_y) + P.refi_bits;
-        if(BI) bits += P.extra_bits;
-        const int sad = acc >> shift;
-        const unsigned cost = ((P.lambda_mv * (unsigned)bits + (1u << 15)) >> 16) + (unsigned)(BI ? sad >> 1 : sad);
-        unsigned long long key = valid ? ((unsigned long long)cost << 32) | (unsigned)(k + 1) : ~0ull;
-        int kb = bits;
-        wave_min_key(key, kb);
-        if(key < best_key) best_key = key, win = (int)(unsigned)key - 1, win_bits = kb;
-    }
-    win = uni(win);
-    if(win >= 0) {
-        cost_best = (unsigned)uni((int)(best_key >> 32)), best_bits = uni(win_bits);
-        int mx = 0, my = 0;
-        (void)gen(win, mx, my);
-        bx = uni(mx), by = uni(my);
-    }
-}
-
-// =========================================================================================================
-// One CANDIDATE per lane.  The mapping above spreads a block over the lanes and pays for it per candidate: a cross-lane sum, the vector cost and a
-// 64-bit cross-group minimum for every 1 .. 8 candidates -- counters (profiles/r02_search_pmc.json): 2 700 VALU + 2 000 SALU instructions per 8x8 job of
-// which ~5 % are v_sad_u16; the kernel is bound by its own bookkeeping, not by any memory level.  Here a lane owns a candidate: it walks the block's
-// rows itself (reference row segment from the plane, original row segment broadcast from a per-wave LDS copy), so a SAD needs no reduction, the vector
-// cost is computed once per candidate, and a round's winner is one 32-bit wave minimum plus a ballot (lanes are in evaluation order, so the lowest
-// lane among the minima is the reference's "first strictly smaller").  The dense (2d+1)^2 round is one pass (two for the 121 candidates of the
-// bi-prediction refinement); the rings that are certain to be evaluated -- the search only stops after `faststep` rounds without improvement -- share
-// one pass as well, and the bookkeeping then consumes their minima ring by ring, in the reference's order.
-// =========================================================================================================
 typedef __attribute__((address_space(3))) const pel lds_cpel;
 
 // the original block (org_bi for the bi-prediction refinement, biased once for the unsigned SAD) into the wave's LDS copy, dense S x S
@@ -459,30 +203,22 @@ __device__ __forceinline__ void cpl_eval(const pel *lorg, const pel *__restrict_
     }
 }
 
-template <int S, bool BI, bool CPL>
+template <int S, bool BI>
 __global__ __launch_bounds__(256) void k_me_diamond(const pel *__restrict__ org0, int s_org, const pel *__restrict__ org_bi,
                                                     const pel *__restrict__ ref0, int s_ref, const xeve_hip_me_job *__restrict__ jobs,
                                                     int njobs, int shift, xeve_hip_me_params P, xeve_hip_me_result *__restrict__ out,
                                                     unsigned long long *__restrict__ units)
 {
-    __shared__ __attribute__((aligned(16))) pel s_lorg[CPL ? 4 * S * S : 8];
+    __shared__ __attribute__((aligned(16))) pel s_lorg[4 * S * S];
     const int lane = threadIdx.x & 63;
     const int j    = xh_xcd_block(blockIdx.x, gridDim.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if(j >= njobs) return;
     const xeve_hip_me_job jb = jobs[j];
     if(jb.range[0] > jb.range[2]) return; // empty range = parked job (its result slot is left untouched)
     unsigned nev = 0;
-    xeve_hip_me_result res;
-    if constexpr(CPL) {
-        pel *lorg = s_lorg + (threadIdx.x >> 6) * (S * S);
-        cpl_load_org<S, BI>(org0, s_org, org_bi, jb.x, jb.y, jb.org_off, lane, lorg);
-        res = cpl_diamond<S, BI>(lorg, ref0, s_ref, jb, shift, P, lane, nullptr, units ? &nev : nullptr);
-    }
-    else {
-        u32x4 org[MGeo<S>::NP];
-        me_load_org<S, BI>(org0, s_org, org_bi, jb.x, jb.y, jb.org_off, lane, org);
-        res = me_diamond<S, BI>(org, ref0, s_ref, jb, shift, P, lane, nullptr, units ? &nev : nullptr);
-    }
+    pel *lorg = s_lorg + (threadIdx.x >> 6) * (S * S);
+    cpl_load_org<S, BI>(org0, s_org, org_bi, jb.x, jb.y, jb.org_off, lane, lorg);
+    const xeve_hip_me_result res = cpl_diamond<S, BI>(lorg, ref0, s_ref, jb, shift, P, lane, nullptr, units ? &nev : nullptr);
     if(lane == 0) out[j] = res;
     if(units && lane == 0) atomicAdd(XH_PROF_SLOT(units), (unsigned long long)nev * (S * S / 64));
 }
@@ -505,12 +241,8 @@ extern "C" int xeve_hip_me_ipel_diamond_jobs(const pel *org0, int s_org, const p
     unsigned long long *units = xh_prof_units(XH_PROF_SEARCH);
 #define ME_LAUNCH(S)                                                                                                          \
     do {                                                                                                                      \
-        if(g_me_cpl) {                                                                                                        \
-            if(P.bi) k_me_diamond<S, true, true><<<grid, 256, 0, st>>>(org0, s_org, org_bi, ref0, s_ref, jobs, njobs, shift, P, results, units);  \
-            else k_me_diamond<S, false, true><<<grid, 256, 0, st>>>(org0, s_org, org_bi, ref0, s_ref, jobs, njobs, shift, P, results, units);     \
-        }                                                                                                                     \
-        else if(P.bi) k_me_diamond<S, true, false><<<grid, 256, 0, st>>>(org0, s_org, org_bi, ref0, s_ref, jobs, njobs, shift, P, results, units);  \
-        else k_me_diamond<S, false, false><<<grid, 256, 0, st>>>(org0, s_org, org_bi, ref0, s_ref, jobs, njobs, shift, P, results, units);     \
+        if(P.bi) k_me_diamond<S, true><<<grid, 256, 0, st>>>(org0, s_org, org_bi, ref0, s_ref, jobs, njobs, shift, P, results, units);  \
+        else k_me_diamond<S, false><<<grid, 256, 0, st>>>(org0, s_org, org_bi, ref0, s_ref, jobs, njobs, shift, P, results, units);     \
     } while(0)
     if(log2w == 3) ME_LAUNCH(8);
     else if(log2w == 4) ME_LAUNCH(16);
@@ -534,18 +266,16 @@ __device__ __forceinline__ void epzs_range(const xeve_hip_me_params &P, int cx, 
 
 // The whole integer stage of pinter_me_epzs by ONE WAVE PER JOB: first search, then refinement searches from the running best while the
 // reference's rule asks for one (xeve_pinter.c:757-822) without leaving the kernel: no
-// launch, no host round trip between the searches, the original block stays in registers across them.
+// launch, no host round trip between the searches, the original block stays in the wave's LDS copy across them.
 // EXTRA: compiled with the branches presets fast / medium never take (me_raster, me_ipel_refinement); the plain form keeps its registers
-template <int S, bool BI, bool EXTRA, int LDSM, bool CPL>
+template <int S, bool BI, bool EXTRA>
 __global__ __launch_bounds__(256) void k_me_epzs(const pel *__restrict__ org0, int s_org, const pel *__restrict__ org_bi, const pel *__restrict__ ref0, int s_ref,
                                                  const xeve_hip_epzs_job *__restrict__ jobs, int njobs, int shift, xeve_hip_me_params P,
                                                  const int32_t *__restrict__ extra, EpzsState *__restrict__ st, XhSearchPlanes pl, int ipel_only,
                                                  unsigned long long *__restrict__ units, xeve_hip_spel_job *__restrict__ sj)
 {
-    __shared__ __attribute__((aligned(16))) pel s_win[LDSM ? 4 * LDSM * MWin<S, BI>::PELS : 8];
-    __shared__ __attribute__((aligned(16))) pel s_lorg[CPL ? 4 * S * S : 8];
-    pel *win = s_win + (threadIdx.x >> 6) * (LDSM * MWin<S, BI>::PELS);
-    pel *lorg = s_lorg + (threadIdx.x >> 6) * (CPL ? S * S : 0);
+    __shared__ __attribute__((aligned(16))) pel s_lorg[4 * S * S];
+    pel *lorg = s_lorg + (threadIdx.x >> 6) * (S * S);
     const int lane = threadIdx.x & 63;
     const int j    = xh_xcd_block(blockIdx.x, gridDim.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if(j >= njobs) return;
@@ -585,24 +315,13 @@ __global__ __launch_bounds__(256) void k_me_epzs(const pel *__restrict__ org0, i
     epzs_range(P, clip3(P.min_clip[0], P.max_clip[0], e.x + (sx >> 2)), clip3(P.min_clip[1], P.max_clip[1], e.y + (sy >> 2)), m.range); // clipped centre (:738-741)
     EpzsState s;
     s.cost = 0xFFFFFFFFu, s.mv[0] = e.mv_start[0], s.mv[1] = e.mv_start[1], s.tmpstep = 0, s.searches = 0, s.mot_bits = 0;
-    u32x4 org[MGeo<S>::NP];
-    if constexpr(CPL) cpl_load_org<S, BI>(org0, s_org, org_bi, e.x, e.y, e.org_off, lane, lorg);
-    else me_load_org<S, BI>(org0, s_org, org_bi, e.x, e.y, e.org_off, lane, org);
-    // the two lane mappings behind one face
-    auto diamond = [&](const xeve_hip_me_job &jb, const xeve_hip_me_params &pp, int *rng, unsigned *ne) {
-        if constexpr(CPL) return cpl_diamond<S, BI>(lorg, ref0, s_ref, jb, shift, pp, lane, rng, ne);
-        else return me_diamond<S, BI, LDSM>(org, ref0, s_ref, jb, shift, pp, lane, rng, ne, win);
-    };
-    auto eval = [&](int nc, auto gen, int gx, int gy, const xeve_hip_me_params &pp, unsigned &cb, int &bb, int &px, int &py) {
-        if constexpr(CPL) cpl_eval<S, BI>(lorg, ref0, s_ref, nc, gen, gx, gy, shift, pp, lane, cb, bb, px, py);
-        else me_eval<S, BI>(org, ref0, s_ref, nc, gen, gx, gy, shift, pp, lane, cb, bb, px, py);
-    };
+    cpl_load_org<S, BI>(org0, s_org, org_bi, e.x, e.y, e.org_off, lane, lorg);
     unsigned nev = 0; // (measurement only; the raster / integer-refinement branches are not counted)
     xeve_hip_me_params Q = P;
     for(int it = 0; it < 64; it++) { // (the reference's loop ends when a search no longer improves; 64 is a safety bound)
         Q.faststep = it == 0 ? 3 : 2; // MAX_FIRST_SEARCH_STEP / MAX_REFINE_SEARCH_STEP
         int rng[4];
-        const xeve_hip_me_result r = diamond(m, Q, rng, units ? &nev : nullptr);
+        const xeve_hip_me_result r = cpl_diamond<S, BI>(lorg, ref0, s_ref, m, shift, Q, lane, rng, units ? &nev : nullptr);
         s.tmpstep = r.beststep, s.searches++;
         if(P.bi != 1 && r.best_mv_bits > 0) s.mot_bits = r.best_mv_bits; // me_ipel_diamond's side effect on pi->mot_bits (:546-548)
         int beststep = 0;
@@ -618,16 +337,16 @@ __global__ __launch_bounds__(256) void k_me_epzs(const pel *__restrict__ org0, i
             const int nx = (rng[2] - rng[0]) / stp + 1, ny = (rng[3] - rng[1]) / stp + 1;
             unsigned rc = 0xFFFFFFFFu;
             int rbits = 0, rx = (r.mv[0] >> 2) + e.x, ry = (r.mv[1] >> 2) + e.y; // (`mv` as the diamond search left it)
-            eval(nx * ny, [&](int k, int &mx, int &my) { mx = rng[0] + (k % nx) * stp, my = rng[1] + (k / nx) * stp; return true; }, m.gmvp[0], m.gmvp[1], Q, rc, rbits,
-                 rx, ry);
+            cpl_eval<S, BI>(lorg, ref0, s_ref, nx * ny, [&](int k, int &mx, int &my) { mx = rng[0] + (k % nx) * stp, my = rng[1] + (k / nx) * stp; return true; }, m.gmvp[0],
+                            m.gmvp[1], shift, Q, lane, rc, rbits, rx, ry);
             for(int ss = (mult * st0) >> 1; ss > 0; ss >>= 1) {
                 const int cx = rx, cy = ry;
-                eval(9,
-                     [&](int k, int &mx, int &my) {
-                         mx = cx + (k % 3 - 1) * ss, my = cy + (k / 3 - 1) * ss;
-                         return mx >= rng[0] && mx <= rng[2] && my >= rng[1] && my <= rng[3];
-                     },
-                     m.gmvp[0], m.gmvp[1], Q, rc, rbits, rx, ry);
+                cpl_eval<S, BI>(lorg, ref0, s_ref, 9,
+                                [&](int k, int &mx, int &my) {
+                                    mx = cx + (k % 3 - 1) * ss, my = cy + (k / 3 - 1) * ss;
+                                    return mx >= rng[0] && mx <= rng[2] && my >= rng[1] && my <= rng[3];
+                                },
+                                m.gmvp[0], m.gmvp[1], shift, Q, lane, rc, rbits, rx, ry);
             }
             if(rbits > 0) s.mot_bits = rbits;
             if(rc < s.cost) beststep = 5, s.cost = rc, s.mv[0] = (int16_t)((rx - e.x) << 2), s.mv[1] = (int16_t)((ry - e.y) << 2); // (:760-767)
@@ -643,14 +362,14 @@ __global__ __launch_bounds__(256) void k_me_epzs(const pel *__restrict__ org0, i
         const int ix = clip3(P.min_clip[0], P.max_clip[0], (s.mv[0] + (e.x << 2)) >> 2), iy = clip3(P.min_clip[1], P.max_clip[1], (s.mv[1] + (e.y << 2)) >> 2);
         unsigned rc = 0xFFFFFFFFu;
         int rbits = 0, rx = ix, ry = iy;
-        eval(9,
-             [&](int k, int &mx, int &my) {
-                 // test_pos (:311): the centre, then x = -1, 0, 1 with y = -1, 0, 1 (the centre left out)
-                 const int q = k == 0 ? 4 : (k <= 4 ? k - 1 : k);
-                 mx = ix + (q / 3 - 1), my = iy + (q % 3 - 1);
-                 return mx >= rg[0] && mx <= rg[2] && my >= rg[1] && my <= rg[3];
-             },
-             m.gmvp[0], m.gmvp[1], P, rc, rbits, rx, ry);
+        cpl_eval<S, BI>(lorg, ref0, s_ref, 9,
+                        [&](int k, int &mx, int &my) {
+                            // test_pos (:311): the centre, then x = -1, 0, 1 with y = -1, 0, 1 (the centre left out)
+                            const int q = k == 0 ? 4 : (k <= 4 ? k - 1 : k);
+                            mx = ix + (q / 3 - 1), my = iy + (q % 3 - 1);
+                            return mx >= rg[0] && mx <= rg[2] && my >= rg[1] && my <= rg[3];
+                        },
+                        m.gmvp[0], m.gmvp[1], shift, P, lane, rc, rbits, rx, ry);
         if(P.bi != 1 && rbits > 0) s.mot_bits = rbits;
         if(rc < s.cost) s.cost = rc, s.mv[0] = (int16_t)((rx - e.x) << 2), s.mv[1] = (int16_t)((ry - e.y) << 2);
     }
@@ -743,27 +462,20 @@ int xh_me_epzs_jobs_planes(const pel *org0, int s_org, const pel *org_bi, const 
         if(ptok) hipExtLaunchKernelGGL((K), grid, dim3(256), 0, st, ev0, ev1, 0, __VA_ARGS__);                     \
         else (K)<<<grid, 256, 0, st>>>(__VA_ARGS__);                                                               \
     } while(0)
-#define EPZS_LAUNCH_M(S, M, C)                                                                                     \
-    do {                                                                                                           \
-        if(extra_branches) {                                                                                       \
-            if(P.bi) EPZS_GO((k_me_epzs<S, true, true, 0, C>), EPZS_ARGS, ipel_only, units, sj_out);               \
-            else EPZS_GO((k_me_epzs<S, false, true, 0, C>), EPZS_ARGS, ipel_only, units, sj_out);                  \
-        }                                                                                                          \
-        else if(P.bi) EPZS_GO((k_me_epzs<S, true, false, M, C>), EPZS_ARGS, 0, units, sj_out);                     \
-        else EPZS_GO((k_me_epzs<S, false, false, M, C>), EPZS_ARGS, 0, units, sj_out);                             \
-    } while(0)
 #define EPZS_LAUNCH(S)                                                                                             \
     do {                                                                                                           \
-        if(g_me_cpl) EPZS_LAUNCH_M(S, 0, true);                                                                    \
-        else if(g_me_lds == 0) EPZS_LAUNCH_M(S, 0, false);                                                         \
-        else EPZS_LAUNCH_M(S, 1, false);                                                                           \
+        if(extra_branches) {                                                                                       \
+            if(P.bi) EPZS_GO((k_me_epzs<S, true, true>), EPZS_ARGS, ipel_only, units, sj_out);                     \
+            else EPZS_GO((k_me_epzs<S, false, true>), EPZS_ARGS, ipel_only, units, sj_out);                        \
+        }                                                                                                          \
+        else if(P.bi) EPZS_GO((k_me_epzs<S, true, false>), EPZS_ARGS, 0, units, sj_out);                           \
+        else EPZS_GO((k_me_epzs<S, false, false>), EPZS_ARGS, 0, units, sj_out);                                   \
     } while(0)
         if(log2w == 3) EPZS_LAUNCH(8);
         else if(log2w == 4) EPZS_LAUNCH(16);
         else if(log2w == 5) EPZS_LAUNCH(32);
         else EPZS_LAUNCH(64);
 #undef EPZS_LAUNCH
-#undef EPZS_LAUNCH_M
 #undef EPZS_GO
 #undef EPZS_ARGS
         if(ptok) xh_prof_end_kernel(ptok);

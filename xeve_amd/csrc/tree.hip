@@ -24,7 +24,6 @@
 #include <cstring>
 #include <vector>
 #include "xh_common.h"
-#include "cu_lane.h"
 
 #define MAX_COST 1.7e+308
 typedef xeve_hip_ctu_data CtuData;
@@ -541,32 +540,6 @@ __global__ void __launch_bounds__(256) k_tree_ops(TreeK K, OpList ops)
     }
 }
 
-// ---- the intra analysis of a 4x4 / 8x8 node: one LANE per chain (cu_lane.h) ------------------------------------------------------------------------------------------
-// 320 of the 341 nodes of an I-picture CTU.  Same inputs and outputs as the batched composite (xeve_hip_pintra_analyze_cu_jobs): the node's job, the chain's entry
-// coder state; result record, dense levels and reconstruction (Y of all chains, then U, then V), core->s_temp_best -- so the tree operations around it do not change.
-template <int LOG2> __global__ void __launch_bounds__(64) k_intra_lane(TreeK K, xl::Params P, const pel *org_y, const pel *org_u, const pel *org_v, const uint8_t *map_tidx,
-                                                                        long org_pic_l, long org_pic_c)
-{
-    // one chain per WAVE, one lane working: the chains of a wave took every branch of this long scalar code one after the other (the writer kernels of encode.hip
-    // met the same wall: 16 chains per wave ran 13 x slower than a wave each)
-    const int c = blockIdx.x, L = LOG2 - 2;
-    if(c >= K.nchains || threadIdx.x != 0) return;
-    const Node *nd = AT(K.node, L);
-    if(!nd->leaf || (K.inter && !nd->try_intra)) return; // (nothing reads the result of a chain whose node is off)
-    const TreeK::Ac &A = K.ac[K.side_of[L]];
-    const xeve_hip_intra_job J = *AT(A.ijobs, L);
-    const int  n0 = 1 << (2 * LOG2), n1 = K.idc ? n0 >> (K.ws + K.hs) : 0;
-    const pel *org[3] = {org_y + J.pic * org_pic_l, org_u ? org_u + J.pic * org_pic_c : nullptr, org_v ? org_v + J.pic * org_pic_c : nullptr};
-    const pel *mod[3] = {K.mod[0] + J.pic * K.mod_pic_l, K.mod[1] ? K.mod[1] + J.pic * K.mod_pic_c : nullptr, K.mod[2] ? K.mod[2] + J.pic * K.mod_pic_c : nullptr};
-    int16_t *coef = const_cast<int16_t *>(A.icoef);
-    pel     *rec = const_cast<pel *>(A.irec);
-    const long oy = (long)c * n0, ou = (long)K.nchains * n0 + (long)c * n1, ov = (long)K.nchains * (n0 + n1) + (long)c * n1;
-    xeve_hip_intra_result R;
-    xl::intra_cu<LOG2>(P, org, mod, K.map_scu + J.pic * K.map_pic, K.map_ipm + J.pic * K.map_pic, map_tidx + J.pic * K.map_pic, *AT(K.curr, L), J, R, coef + oy, coef + ou, coef + ov,
-                       rec + oy, rec + ou, rec + ov, A.sbest[c]);
-    const_cast<xeve_hip_intra_result *>(A.ires)[c] = R;
-}
-
 // ---- host ------------------------------------------------------------------------------------------------------------------------------------------------
 extern "C" int xeve_hip_satd_jobs(const pel *p1, int s1, const pel *p2, int s2, const xeve_hip_job *jobs, int njobs, const int32_t *cand_off, int ncand, int w, int h,
                                   int bit_depth, int32_t *out, void *stream);
@@ -616,25 +589,6 @@ static xeve_hip_inter_params level_inter_params(const xeve_hip_tree_inter *I, in
     xeve_hip_inter_params ep = I->ipar;
     ep.rdo.log2_cuw = ep.rdo.log2_cuh = log2;
     return ep;
-}
-static xl::Params lane_params(const xeve_hip_tree_params *p, int log2, int s_org_l, int s_org_c, int s_mod_l, int s_mod_c)
-{
-    static const int q_scale[6] = {26214, 23302, 20560, 18396, 16384, 14764}, dq_scale[6] = {40, 45, 51, 57, 64, 71}; // xeve_quant_scale[0] (xeve_tq.c:37), xeve_tbl_dq_scale_b (xeve_tbl.c:237)
-    xl::Params P;
-    const xeve_hip_intra_params &ip = p->ip;
-    const int idc = ip.chroma_format_idc, bd = ip.bit_depth, lc = log2 - (idc <= 2 ? 1 : 0);
-    P.idc = idc, P.bd = bd, P.slice_type = ip.slice_type, P.cip = ip.constrained_intra_pred != 0, P.w_scu = ip.w_scu, P.h_scu = ip.h_scu;
-    P.s_org_l = s_org_l, P.s_org_c = s_org_c, P.s_mod_l = s_mod_l, P.s_mod_c = s_mod_c;
-    for(int c = 0; c < 3; c++) {
-        const int q = ip.qp[c], log2_size = c ? lc : log2, tr_shift = 15 - bd - log2_size;
-        P.qp[c] = q, P.q_scale[c] = q_scale[q % 6], P.dq_scale[c] = dq_scale[q % 6] << (q / 6), P.lambda[c] = ip.lambda[c];
-        double e = (double)(1 << 15) * pow(2.0, -tr_shift); // ctx->err_scale[qp % 6][log2_size - 1], xeve_init_err_scale (xeve_tq.c:406-423)
-        e = e / q_scale[q % 6] / (1 << (bd - 8));
-        P.err_scale[c] = (int64_t)(e * (double)(1 << 20));
-    }
-    P.sqrt_lambda0 = ip.sqrt_lambda0, P.wgt[0] = ip.dist_chroma_weight[0], P.wgt[1] = ip.dist_chroma_weight[1];
-    P.entropy = xh_entropy_table();
-    return P;
 }
 // a node of this size can be a CU at all: within max_cu and no larger than the picture (the analyses of a size the picture cannot hold are left out of the schedule)
 static bool level_has_cu(const xeve_hip_tree_params *p, int log2) { return (1 << log2) <= p->max_cu && (1 << log2) <= p->pic_w && (1 << log2) <= p->pic_h; }
@@ -728,40 +682,6 @@ extern "C" size_t xeve_hip_mode_analyze_ctu_intra_workspace(int nchains, const x
 }
 
 namespace {
-struct TreeGraph {
-    std::vector<char> key;
-    int               seen  = 0;
-    hipGraph_t        graph = nullptr;
-    hipGraphExec_t    exec  = nullptr;
-};
-struct TreeGraphs { // per thread; dropped when the library is re-bound
-    uint32_t               gen = 0;
-    std::vector<TreeGraph> v;
-    void drop()
-    {
-        if(!v.empty()) (void)hipDeviceSynchronize(); // (a replay may still be in flight)
-        for(auto &g : v) {
-            if(g.exec) (void)hipGraphExecDestroy(g.exec);
-            if(g.graph) (void)hipGraphDestroy(g.graph);
-        }
-        v.clear();
-    }
-    TreeGraph *find(const std::vector<char> &key)
-    {
-        if(gen != xh_generation()) drop(), gen = xh_generation();
-        for(auto &g : v)
-            if(g.key == key) return &g;
-        return nullptr;
-    }
-    void add(const std::vector<char> &key)
-    {
-        if(v.size() >= 64) drop(); // (a batch encoder's walk: I and P / B pictures x the chain counts of a wavefront's ramp = a few dozen distinct calls)
-        TreeGraph g;
-        g.key = key;
-        v.push_back(std::move(g));
-    }
-    ~TreeGraphs() { drop(); }
-};
 enum { AN_NONE = 0, AN_INTRA = 1, AN_INTER = 2 };
 // one entry of the schedule: [wait for an event] [tree operations] [an analysis] [record an event], all on one of the call's two streams
 struct Item {
@@ -905,12 +825,11 @@ extern "C" int xeve_hip_mode_analyze_ctu_jobs(const xeve_hip_pel *const org[3], 
         return xh_walk_run(org, s_org_l, s_org_c, mod, s_mod_l, s_mod_c, map_scu, map_ipm, map_tidx, map_cu_mode, pic_elems, states, p, I, jobs, nchains, out, next_best, cost,
                            workspace, workspace_bytes, vh, (hipStream_t)stream);
     hipStream_t st = (hipStream_t)stream;
-    // the side stream: unless switched off, the caller is capturing its stream into a graph, or the walk replays from a graph of its own
-    static const int use_graph = getenv("XEVE_HIP_TREE_GRAPH") ? atoi(getenv("XEVE_HIP_TREE_GRAPH")) : 0;
+    // the side stream: unless switched off or the caller is capturing its stream into a graph
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if(st) (void)hipStreamIsCapturing(st, &cap);
     static thread_local TreeSide side_res;
-    const int side = !use_graph && cap == hipStreamCaptureStatusNone && side_res.ready() ? g_tree_side.load(std::memory_order_relaxed) : 0;
+    const int side = cap == hipStreamCaptureStatusNone && side_res.ready() ? g_tree_side.load(std::memory_order_relaxed) : 0;
     const TreeLayout L = tree_layout(nchains, p, I, s_org_l, s_org_c, side);
     XH_REQUIRE(workspace_bytes >= L.total);
     char       *W = (char *)workspace;
@@ -945,12 +864,6 @@ extern "C" int xeve_hip_mode_analyze_ctu_jobs(const xeve_hip_pel *const org[3], 
     wk.add(OP_ROOT_DONE, p->log2_ctu - 2, 0);
     wk.flush(AN_NONE, 0);
     const pel *const modc[3] = {mod[0], mod[1], mod[2]};
-    // XEVE_HIP_TREE_LANE=1: the 4x4 / 8x8 nodes decided by one lane per chain (cu_lane.h, k_intra_lane) instead of the batched composite.  MEASURED
-    // (profiles/r02_tree_lane.log): 3 launches per node instead of 29 and 3.5 ms of host time per CTU step instead of 56, but the serial lane code runs ~ 560 us per
-    // node (a single wave issues one dependent instruction every ~ 9 cycles and the chains of a wave diverge): 179 ms per CTU step for one chain against 68 ms, 583 ms
-    // against 217 ms for 8192 chains.  It only pays with >= 8 waves per SIMD, i.e. >= 65 000 chains in flight.  OFF by default; kept because it is the bit-exact,
-    // CPU-tested (tests/test_cu_lane.py) starting point of a wave-per-chain node kernel.
-    static const int use_lane = getenv("XEVE_HIP_TREE_LANE") ? atoi(getenv("XEVE_HIP_TREE_LANE")) : 0;
     XH_REQUIRE(xh_entropy_table() != nullptr);
     auto enqueue = [&]() -> int { // the whole walk: on `st`, and on the side stream between the events
         XH_HIP(hipMemsetAsync(W + L.zero_from, 0, L.zero_bytes, st)); // the walk's own state starts from zero (a node the picture cuts leaves its outside part untouched)
@@ -980,17 +893,11 @@ extern "C" int xeve_hip_mode_analyze_ctu_jobs(const xeve_hip_pel *const org[3], 
             // core->rdoq_est_* of the node's entry states (xeve_mode.c:792): once per node, for its inter analysis' two pinter_residue_rdo batches and its intra analysis
             // (round 6: each of the three made its own)
             auto *est = (xeve_hip_rdoq_est_full *)(W + LA.est);
-            if(it.kind == AN_INTER || (it.kind == AN_INTRA && !I && !(log2 <= 3 && use_lane))) {
+            if(it.kind == AN_INTER || (it.kind == AN_INTRA && !I)) {
                 rc = xeve_hip_rdoq_bit_est(K.curr + (size_t)(log2 - 2) * nchains, nchains, est, sv);
                 if(rc != XEVE_HIP_OK) return rc;
             }
-            if(it.kind == AN_INTRA && log2 <= 3 && use_lane) { // one lane per chain decides the node (cu_lane.h)
-                const xl::Params LP = lane_params(p, log2, s_org_l, s_org_c, s_mod_l, s_mod_c);
-                const int grid = nchains;
-                if(log2 == 2) k_intra_lane<2><<<grid, 64, 0, s>>>(K, LP, org[0], org[1], org[2], map_tidx, pic_elems ? pic_elems[0] : 0, pic_elems ? pic_elems[1] : 0);
-                else k_intra_lane<3><<<grid, 64, 0, s>>>(K, LP, org[0], org[1], org[2], map_tidx, pic_elems ? pic_elems[0] : 0, pic_elems ? pic_elems[1] : 0);
-            }
-            else if(it.kind == AN_INTRA) {
+            if(it.kind == AN_INTRA) {
                 const xeve_hip_intra_params ip = level_params(p, log2);
                 rc = xh_pintra_analyze_cu_jobs_x(org, s_org_l, s_org_c, modc, s_mod_l, s_mod_c, map_scu, map_ipm, map_tidx, pic_elems, K.curr + (size_t)(log2 - 2) * nchains,
                                                  nchains, &ip, A.ijobs + (size_t)(log2 - 2) * nchains, nchains, (xeve_hip_intra_result *)(W + LA.ires), (int16_t *)(W + LA.icoef), (pel *)(W + LA.irec), A.sbest,
@@ -1019,36 +926,6 @@ extern "C" int xeve_hip_mode_analyze_ctu_jobs(const xeve_hip_pel *const org[3], 
         }
         return XEVE_HIP_OK;
     };
-    // The schedule is static (10 000 launches per I-picture CTU, 15 600 per P / B CTU) and every operand sits at an address the caller chose, so a call whose
-    // arguments repeat can be captured into a HIP graph and replayed.  MEASURED (profiles/r02_tree_graph.log): the replay frees the host -- 2.8 ms instead of
-    // 56 .. 100 ms of launch calls per CTU step -- but the GPU runs the same step 8 .. 10 ms SLOWER (dependent kernel nodes of a graph dispatch no faster than
-    // stream launches here), so it is OFF unless XEVE_HIP_TREE_GRAPH=1: for a caller that needs its host thread, not for speed.
-    if(use_graph && st && cap == hipStreamCaptureStatusNone && !xh_prof_on(XH_PROF_SEARCH) && !xh_prof_on(XH_PROF_CU_BITS)) {
-        static thread_local TreeGraphs G;
-        std::vector<char> key;
-        auto put = [&](const void *a, size_t n) { key.insert(key.end(), (const char *)a, (const char *)a + n); };
-        const void *ptrs[] = {org[0], org[1], org[2], mod[0], mod[1], mod[2], map_scu, map_ipm, map_tidx, map_cu_mode, states, jobs, out, next_best, cost, workspace, stream};
-        const long  ints[] = {s_org_l, s_org_c, s_mod_l, s_mod_c, nstates, nchains, (long)workspace_bytes, pic_elems ? 1 : 0};
-        put(ptrs, sizeof(ptrs)), put(ints, sizeof(ints)), put(p, sizeof(*p));
-        if(pic_elems) put(pic_elems, 5 * sizeof(int64_t));
-        if(I) put(I, sizeof(*I)), put(I->refp, sizeof(xeve_hip_refpic) * 2 * (size_t)std::max(I->ipar.rdo.num_refp[0], I->ipar.rdo.num_refp[1]));
-        TreeGraph *g = G.find(key);
-        if(g && g->exec) {
-            XH_HIP(hipGraphLaunch(g->exec, st));
-            return XEVE_HIP_OK;
-        }
-        if(g && ++g->seen >= 2) {
-            XH_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            const int        rc = enqueue();
-            const hipError_t ec = hipStreamEndCapture(st, &g->graph);
-            if(rc != XEVE_HIP_OK) return rc;
-            XH_HIP(ec);
-            XH_HIP(hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0));
-            XH_HIP(hipGraphLaunch(g->exec, st));
-            return XEVE_HIP_OK;
-        }
-        if(!g) G.add(key);
-    }
     const int rc = enqueue();
     if(rc != XEVE_HIP_OK) return rc;
     XH_HIP(hipGetLastError());

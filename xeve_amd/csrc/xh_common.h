@@ -11,11 +11,9 @@ typedef int16_t pel;
 // ---- DEVELOPER SWITCHES (environment, read once per process; results never depend on them: tests/test_dev_switches_gpu.py runs a reference-bitstream case under each) ------
 //   XEVE_HIP_WALK = 0 | 1 | auto, XEVE_HIP_WALK_AUTO_MAX = n       which CTU walk (composed / fused / by width: fused up to n chains, 0 since round 6); xeve_hip_walk_select
 //   XEVE_HIP_TREE_SIDE = 0 | 1 | 2                                 the composed walk on one stream / with its side stream (default) / a side stream per node size; xeve_hip_walk_side
-//   XEVE_HIP_TREE_GRAPH = 1, XEVE_HIP_TREE_LANE = 1                the one-stream walk replayed from a HIP graph; 4x4 / 8x8 intra nodes by the lane-serial kernel (both measured slower)
 //   XEVE_HIP_RDO_SPEC = n                                          pinter_residue_rdo's four bit-count rounds as one speculative round for batches of up to n candidates (256)
-//   XEVE_HIP_ME_CPL = 0, XEVE_HIP_ME_LDS = 1                       the search kernel's older lane mappings (rows per lane; the LDS-staged window)
 //   XEVE_HIP_DCT = valu                                            32x32 / 64x64 transforms on the VALU path instead of the matrix cores
-//   XEVE_HIP_WRITER_WAVE = 0, XEVE_HIP_ENC_TWO_STORES = 0          the entropy writer on a lone lane; one CTU store instead of two
+//   XEVE_HIP_ENC_TWO_STORES = 0                                    one CTU store instead of two
 //   XEVE_HIP_ENC_PRIO = 1, XEVE_HIP_ENC_FULL_STATES = 1            the encoder's main stream above its second-pass stream; complete coder states through the walk
 //   XEVE_HIP_ENC_SHARE = 0                                         every picture store in memory of its own (default: later stores over the frames already coded, encode.hip)
 //   XEVE_HIP_HOST_GRAPH = 0                                        the host-memory form of the inter analysis without its per-CU graph replay
