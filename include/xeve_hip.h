@@ -938,6 +938,10 @@ int xeve_hip_enc_stats(xeve_hip_enc *e, int64_t *ctu_steps, double *step_seconds
  * walk's workspace).  No device call: usable before xeve_hip_init.  A job larger than one batch is several xeve_hip_enc objects, a host thread each -- the device runs
  * their launch chains side by side (xeve_amd/encode.py encode_gops does the split). */
 int xeve_hip_enc_footprint(const xeve_hip_enc_config *cfg, int ngops, int frames, uint64_t *device_bytes, int32_t *max_gops);
+/* The bytes one picture's slice data may take (per run; part of the footprint): at least w * h * 3 / 2 + 4096, more where the run's lowest slice QP -- cfg->qp with the
+ * hierarchy's offsets over the pictures `frames` frames make -- is so low that a picture of noise would not fit (below 24 at 3840x2160; 7.5 bytes per sample at QP 0).
+ * A picture that still outgrows it ends the run with an error, never with a write past the buffer.  No device call. */
+int xeve_hip_enc_slice_capacity(const xeve_hip_enc_config *cfg, int frames, uint64_t *bytes);
 
 /* ------------------------------------------------------------------------------------------- */
 /* Main profile: the adaptive loop filter's sample kernels ("ALF           */

@@ -1281,6 +1281,11 @@ const uint8_t xo_df_st[4][52] = { /* xeve_tbl.c:239-257: intra; luma cbf; mv dif
     {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 4, 4, 5, 6, 7, 8, 9, 10, 10, 10, 10, 10},
     {0}};
 
+/* a chroma edge's strength: xeve_tbl_df_st[class][chroma QP] as the reference's arithmetic reads it when the QP is negative (10-bit pictures, slice QP + chroma offset
+ * < 0: the chroma table is the identity there) -- classes 1 .. 3 the tail of the row before, class 0 what lies in front of the table: zero padding in the reference
+ * build (written out here; reading in front of xo_df_st would depend on this library's layout) */
+static int df_st_chroma(int cls, int q) { return q >= 0 ? xo_df_st[cls][q] : (cls > 0 && q >= -52 ? xo_df_st[cls - 1][52 + q] : 0); }
+
 #define SCU_IF(m)   (((m) >> 15) & 1)
 #define SCU_QP(m)   (((m) >> 16) & 0x7F)
 #define SCU_CBFL(m) (((m) >> 24) & 1)
@@ -1354,7 +1359,7 @@ static void df_segment(const df_ctx *c, int cur, int nb, int x, int y, int hor)
     if(p->chroma_format_idc) {
         int qu = clip3i(-6 * bc, 57, qp + p->qp_u_offset), qv = clip3i(-6 * bc, 57, qp + p->qp_v_offset);
         int off = (y >> c->hs) * c->s_c + (x >> c->ws);
-        int st_u = xo_df_st[cls][p->qp_chroma[0][qu + 6 * bc]] << bc, st_v = xo_df_st[cls][p->qp_chroma[1][qv + 6 * bc]] << bc;
+        int st_u = df_st_chroma(cls, p->qp_chroma[0][qu + 6 * bc]) << bc, st_v = df_st_chroma(cls, p->qp_chroma[1][qv + 6 * bc]) << bc;
         /* the reference sizes the chroma segment with the W shift for horizontal and the H shift for vertical edges (xeve_df.c:143,225) */
         if(hor) df_edge(c->u + off, 4 >> c->ws, 1, c->s_c, st_u, (1 << p->bit_depth_chroma) - 1, 1), df_edge(c->v + off, 4 >> c->ws, 1, c->s_c, st_v, (1 << p->bit_depth_chroma) - 1, 1);
         else df_edge(c->u + off, 4 >> c->hs, c->s_c, 1, st_u, (1 << p->bit_depth_chroma) - 1, 1), df_edge(c->v + off, 4 >> c->hs, c->s_c, 1, st_v, (1 << p->bit_depth_chroma) - 1, 1);
@@ -1472,7 +1477,7 @@ void xo_delta_dist(const xo_dbk_ctx *D, const xo_pel *const org[3], int s_org_l,
                 if(c == 0) df_edge(dst + 4 * i, 4, 1, S, xo_df_st[cls][qp] << bl, maxv, 0);
                 else {
                     const int q = clip3i(-6 * bc, 57, qp);
-                    df_edge(dst + ((4 * i) >> ws), 4 >> ws, 1, S, xo_df_st[cls][p->qp_chroma[c - 1][q + 6 * bc]] << bc, maxv, 1);
+                    df_edge(dst + ((4 * i) >> ws), 4 >> ws, 1, S, df_st_chroma(cls, p->qp_chroma[c - 1][q + 6 * bc]) << bc, maxv, 1);
                 }
             }
         if(left)
@@ -1482,7 +1487,7 @@ void xo_delta_dist(const xo_dbk_ctx *D, const xo_pel *const org[3], int s_org_l,
                 if(c == 0) df_edge(dst + (size_t)(4 * i) * S, 4, S, 1, xo_df_st[cls][qp] << bl, maxv, 0);
                 else {
                     const int q = clip3i(-6 * bc, 57, qp);
-                    df_edge(dst + (size_t)((4 * i) >> hs) * S, 4 >> hs, S, 1, xo_df_st[cls][p->qp_chroma[c - 1][q + 6 * bc]] << bc, maxv, 1);
+                    df_edge(dst + (size_t)((4 * i) >> hs) * S, 4 >> hs, S, 1, df_st_chroma(cls, p->qp_chroma[c - 1][q + 6 * bc]) << bc, maxv, 1);
                 }
             }
         int64_t after = xo_ssd(w, h, dst, o, S, so, bd);

@@ -7,7 +7,7 @@ from _libs import DeblockParams
 PAD = 16
 
 
-def make_case(r, w, h, bd=10, idc=1, min_cu=4, log2_ctu=6):
+def make_case(r, w, h, bd=10, idc=1, min_cu=4, log2_ctu=6, qp_range=(18, 52)):
     ws, hs = (1 if idc <= 2 else 0), (1 if idc <= 1 else 0)
     w_scu, h_scu = (w + 3) // 4, (h + 3) // 4
     s_l, s_c = w + 2 * PAD, (w >> ws) + 2 * PAD
@@ -28,7 +28,7 @@ def make_case(r, w, h, bd=10, idc=1, min_cu=4, log2_ctu=6):
     def leaf(x, y, size):
         sx, sy, n = x // 4, y // 4, size // 4
         lg = size.bit_length() - 1
-        intra, cbfl, qp = int(r.random() < 0.15), int(r.random() < 0.5), int(r.integers(18, 52))
+        intra, cbfl, qp = int(r.random() < 0.15), int(r.random() < 0.5), int(r.integers(*qp_range))
         m = (int(r.integers(0, 1 << 15))) | (intra << 15) | (qp << 16) | (cbfl << 24)  # low bits: fields the filter must ignore
         rf = (-1, -1) if intra else [(0, -1), (-1, 0), (0, 0), (1, 0), (0, 1), (1, -1)][int(r.integers(0, 6))]
         v = r.integers(-9, 10, size=(2, 2)) if r.random() < 0.7 else r.integers(-2, 3, size=(2, 2))

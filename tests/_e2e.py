@@ -68,9 +68,12 @@ REAL_CASES = {
 
 def make_yuv(path, w, h, frames, seed):
     """seeds below 5000: i.i.d. noise (SURVEY.md 8d recipe); from 5000: a smooth texture drifting over the frames plus light noise -- content on
-    which skip / merge, temporal direct and bi-prediction actually win"""
+    which skip / merge, temporal direct and bi-prediction actually win; 9000 .. 9255: every sample of every plane = seed - 9000 (saturated content: flat 0, flat 255)"""
     import numpy as np
 
+    if 9000 <= seed <= 9255:
+        np.full(w * h * 3 // 2 * frames, seed - 9000, dtype=np.uint8).tofile(path)
+        return
     random.seed(seed)
     if seed < 5000:  # bytes(random.getrandbits(8) ...) without the Python loop: getrandbits(8) is the top byte of one MT19937 output, and numpy's legacy generator runs
         # the same twister from the same state (tests/test_bench_inputs.py holds the two against each other)

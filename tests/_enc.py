@@ -193,6 +193,38 @@ PRESET_REAL_CASES = {
     "slow_1080p_noise_3f_m8": (1920, 1080, 1, 3, 3, ["--preset", "slow", "--closed-gop", "-I", "8"], 8),
     "placebo_1080p_moving_3f_m8": (1920, 1080, 1, 3, 5049, ["--preset", "placebo", "--closed-gop", "-I", "8"], 8),
 }
+# The ends of the accepted QP range (Param::finish takes -q 0 .. 51), all at 128x64 unless said -- two CTUs, every picture type.  A picture whose slice QP is 0 is
+# quantised by the reference at QP 1 (get_min_max_qp clips the CU's QP to 1 .. 51, xeve_mode.c:753-754) while its header, lambdas and chroma weights stay at 0; the
+# hierarchy's offsets clip at 51; the chroma table is entered below 0 (identity) and clipped at 57.  Cases with --qp-c?-offset / --inter-slice-type reach the reference
+# library through oracle/ref_param_pin.c as HOST_PINNED_CASES do; "-d 10" cases are fed widen10's samples; seeds 9000 + v: flat frames of value v (tests/_e2e.py).
+QP_RANGE_CASES = {
+    # slice QP 0 and its neighbours
+    "q0_noise_closed": (128, 64, 2, 4, 21, ["--preset", "medium", "--closed-gop", "-I", "4", "-b", "3", "-q", "0"], 1),
+    "q0_moving_ldb": (128, 64, 1, 3, 5021, ["--preset", "fast", "-I", "0", "-b", "0", "-q", "0"], 1),
+    "q1_moving_ldb": (128, 64, 1, 3, 5021, ["--preset", "fast", "-I", "0", "-b", "0", "-q", "1"], 1),  # (the low-delay table's layer offset -1: only the I picture is at QP 0)
+    "q1_noise_allintra": (128, 64, 1, 3, 21, ["--preset", "fast", "-I", "1", "-b", "0", "-q", "1"], 1),  # the control: nothing is clamped
+    "q2_moving_ra": (128, 64, 1, 4, 5021, ["--preset", "medium", "-b", "1", "-q", "2"], 1),
+    "q0_moving_m2": (128, 128, 1, 3, 5021, ["--preset", "fast", "-I", "0", "-b", "0", "-q", "0"], 2),  # two row chains, the second writer pass
+    # the top of the range
+    "q51_noise_closed": (128, 64, 2, 4, 21, ["--preset", "medium", "--closed-gop", "-I", "4", "-b", "3", "-q", "51"], 1),
+    "q51_moving_ra_b3": (128, 64, 1, 5, 5021, ["--preset", "medium", "-b", "3", "-q", "51"], 1),  # every layer offset clips at 51
+    "q48_moving_ra_b3": (128, 64, 1, 5, 5021, ["--preset", "medium", "-b", "3", "-q", "48"], 1),  # only the deeper layers clip
+    # the chroma tables at their ends: a negative index (the identity branch), the clip at 57
+    "q0_cb-12_cr+12": (128, 64, 1, 4, 5021, ["--preset", "medium", "-b", "1", "-q", "0", "--qp-cb-offset", "-12", "--qp-cr-offset", "12"], 1),
+    "q5_cb-12_cr-7_p": (128, 64, 1, 4, 5021, ["--preset", "fast", "-b", "0", "-q", "5", "--qp-cb-offset", "-12", "--qp-cr-offset", "-7", "--inter-slice-type", "1"], 1),
+    "q51_cb+12_cr-12": (128, 64, 1, 4, 5021, ["--preset", "medium", "-b", "1", "-q", "51", "--qp-cb-offset", "12", "--qp-cr-offset", "-12"], 1),
+    "q47_cb+12_cr+3_b3": (128, 64, 1, 5, 5021, ["--preset", "medium", "-b", "3", "-q", "47", "--qp-cb-offset", "12", "--qp-cr-offset", "3"], 1),
+    # presets slow and placebo (the fused walk only)
+    "slow_q0_moving_ldb": (128, 64, 1, 3, 5021, ["--preset", "slow", "-I", "0", "-b", "0", "-q", "0"], 1),
+    "slow_q51_moving_ra": (128, 64, 1, 4, 5021, ["--preset", "slow", "-b", "1", "-q", "51"], 1),
+    "placebo_q0_moving_ldb": (128, 64, 1, 3, 5021, ["--preset", "placebo", "-I", "0", "-b", "0", "-q", "0"], 1),
+    "placebo_q51_noise_ra": (128, 64, 1, 4, 21, ["--preset", "placebo", "-b", "1", "-q", "51"], 1),
+    # 10-bit input
+    "q0_10bit_noise": (128, 64, 1, 3, 21, ["--preset", "fast", "-I", "0", "-b", "0", "-q", "0", "-d", "10"], 1),
+    # saturated content
+    "q0_flat255": (128, 64, 1, 3, 9255, ["--preset", "medium", "-b", "1", "-q", "0"], 1),
+    "q51_flat0": (128, 64, 1, 3, 9000, ["--preset", "medium", "-b", "1", "-q", "51"], 1),
+}
 # What the PRODUCT library's configuration check (enc_plan.h Param::finish) takes and what it refuses -- ONE table, read by tests/test_enc_host.py through
 # xeve_hip_enc_footprint (no device: a change of the accepted set fails in the build container) and by tests/test_enc_gpu.py through xeve_hip_enc_create.
 # (kwargs of xeve_amd.encode.config beside w / h, accepted?)
@@ -237,6 +269,22 @@ def widen10(data8):
 
     b = np.frombuffer(data8, dtype=np.uint8).astype(np.uint16)
     return ((b << 2) | ((b * 3 + np.arange(b.size, dtype=np.uint16)) & 3)).astype("<u2").tobytes()
+
+
+def qp_range_input(yuv_dir, name):
+    """the input of a QP_RANGE_CASES entry as the encoders take it: one bytes object per GOP (16-bit samples where the options say -d 10)"""
+    import _e2e
+
+    w, h, gops, frames, seed, cli, _ = QP_RANGE_CASES[name]
+    p = os.path.join(yuv_dir, name + ".yuv")
+    if not os.path.exists(p):
+        _e2e.make_yuv(p, w, h, gops * frames, seed)
+    data = open(p, "rb").read()
+    if "-d" in cli:
+        assert cli[cli.index("-d") + 1] == "10"
+        data = widen10(data)
+    fb = len(data) // gops
+    return [data[i * fb:(i + 1) * fb] for i in range(gops)]
 
 
 def golden():

@@ -27,6 +27,8 @@ assert C.sizeof(TreeParams) == 136 and CTU_DATA_DTYPE.itemsize == 62976
 # seed, pictures, w, h, bit depth, chroma_format_idc, log2 CTU, max_cu_intra, min_cu_intra, qp
 CASES = [(3101, 3, 128, 64, 10, 1, 6, 32, 4, 37), (3102, 2, 72, 88, 10, 1, 6, 64, 4, 30), (3103, 2, 64, 64, 8, 0, 5, 32, 8, 42), (3104, 2, 96, 64, 10, 3, 6, 32, 4, 34),
          (3105, 2, 64, 32, 10, 1, 4, 16, 4, 27)]
+# the ends of the QP range (a list of its own: tests/golden/tree_v1.npz records CASES): QP 1 -- what a slice of QP 0 or 1 is quantised at, levels in the thousands -- and 51
+QP_EDGE_CASES = [(3111, 2, 128, 64, 10, 1, 6, 32, 4, 1), (3112, 2, 128, 64, 10, 1, 6, 32, 4, 51)]
 
 
 def make_case(seed, npic, w, h, bd, idc, log2_ctu, max_cu, min_cu, qp8):

@@ -23,6 +23,7 @@ def test_library_exports_every_declared_symbol():
     L = lib.load()
     funcs, tables = declared_symbols()
     assert len(funcs) >= 20 and len(tables) == 16
+    assert "xeve_hip_enc_footprint" in funcs and "xeve_hip_enc_slice_capacity" in funcs  # (what a batch costs, readable without a device)
     for name in funcs + tables:
         assert C.c_void_p.in_dll(L, name) is not None, name
     # and the Python binding covers exactly the same set

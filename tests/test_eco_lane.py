@@ -119,6 +119,44 @@ def test_lane_tile_end_matches_oracle():
     assert len(kinds) >= 3
 
 
+def test_lane_writer_stores_nothing_beyond_its_capacity_and_still_counts():
+    """xl::Sink bounds-checks every store (what makes a picture that outgrows its slice buffer an error and not a corruption, encode.hip): a CTU written with a capacity
+    below its length -- half, one byte, none, and the negative rest a buffer that is already full hands the next CTU -- stores the prefix, touches nothing at or beyond the
+    capacity, and reports the full length; the coder state left behind does not depend on the capacity.  The same for the tile's end."""
+    L, sc = _lane.lane(), _lane.scans()
+    case = CASES[0]
+    c = make_case(*case)
+    O = oracle_tree()
+    org = (c_void_p * 3)(*[a[0].ctypes.data for a in c["org"]])
+    mod = (c_void_p * 3)(*[a[0].ctypes.data for a in c["mod"]])
+    m, P = c["maps"], c["P"]
+    state = c["entry"][0:1].copy()
+    state["bitcounter"] = 0
+    x, y = c["order"][0]
+    d, nb = np.zeros(1, CTU_DATA_DTYPE), np.zeros(1, SBAC_DTYPE)
+    O.xo_mode_analyze_ctu_intra(org, c["org"][0].shape[2], c["org"][1].shape[2], mod, c["mod"][0].shape[2], c["mod"][1].shape[2], ptr(m["scu"][0]), ptr(m["ipm"][0]),
+                                ptr(m["tidx"][0]), ptr(m["cu_mode"][0]), ptr(state), C.byref(P), x, y, ptr(d), ptr(nb))
+
+    def write(cap):
+        scu, cum, st, out = m["scu"][0].copy(), m["cu_mode"][0].copy(), state.copy(), np.full(1 << 16, 0xA5, np.uint8)
+        n = L.xl_host_eco_ctu(P.ip.chroma_format_idc, P.ip.slice_type, P.log2_ctu, P.pic_w, P.pic_h, P.ip.w_scu, 0, 0, ptr(sc[0]), ptr(sc[1]), ptr(sc[2]), ptr(st), ptr(d), ptr(scu),
+                              ptr(m["ipm"][0]), ptr(m["tidx"][0]), ptr(cum), x, y, ptr(out), cap)
+        return n, out, st
+
+    full_n, full, full_st = write(1 << 16)
+    assert 100 < full_n < (1 << 15) and not np.all(full[:full_n] == 0xA5)
+    for cap in (full_n // 2, full_n - 1, 1, 0, -7):
+        n, out, st = write(cap)
+        keep = max(cap, 0)
+        assert n == full_n and np.array_equal(out[:keep], full[:keep]) and np.all(out[keep:] == 0xA5), cap
+        assert st.tobytes() == full_st.tobytes(), cap
+    end_n, end, _ = (lambda s, b: (L.xl_host_eco_tile_end(ptr(s), ptr(b), 64), b, s))(full_st.copy(), np.full(64, 0xA5, np.uint8))
+    assert end_n >= 2
+    for cap in (end_n - 1, 0, -3):
+        b = np.full(64, 0xA5, np.uint8)
+        assert L.xl_host_eco_tile_end(ptr(full_st.copy()), ptr(b), cap) == end_n and np.array_equal(b[:max(cap, 0)], end[:max(cap, 0)]) and np.all(b[max(cap, 0):] == 0xA5), cap
+
+
 def test_lane_writer_on_more_pictures():
     """more seeds: 4:4:4 and 4:0:0 I pictures with partial CTUs, B pictures with two reference pictures per list and both early-termination depths"""
     for case in [(3201, 2, 104, 72, 10, 3, 6, 64, 4, 28), (3202, 2, 72, 104, 8, 0, 6, 32, 8, 36), (3203, 1, 96, 96, 10, 1, 5, 32, 4, 24)]:

@@ -52,6 +52,38 @@ def test_a_job_is_cut_into_rounds_of_batches_that_fit():
         encode.plan_batches(c, 5, 2, 1 << 20)
 
 
+def test_the_slice_buffer_is_sized_by_the_runs_lowest_slice_qp():
+    """tests/golden/slice_bytes_v1.json (make_slice_bytes_golden.py): what the unmodified reference spends on a picture of i.i.d. noise at every -q, 128x64 all-intra.  A
+    picture's slice buffer holds 1.25 x that rate at 128x64 and at 3840x2160 -- the margin covers the rate's dependence on the picture size and B pictures coded slightly
+    above the I picture's rate on noise -- and stays w * h * 3 / 2 + 4096 wherever that already does (-q 32, the benchmark's, among them: its footprint must not move)"""
+    import json
+    import os
+
+    t = json.load(open(os.path.join(_enc.ROOT, "tests", "golden", "slice_bytes_v1.json")))
+    assert [r["q"] for r in t["per_q"]] == list(range(52)) and t["samples_per_picture"] == 128 * 64 * 3 // 2
+    kept = {}
+    for w, h in ((128, 64), (3840, 2160)):
+        samples, before = w * h * 3 // 2, w * h * 3 // 2 + 4096
+        for r in t["per_q"]:
+            assert r["bytes_per_sample"] == max(r["slice_bytes"]) / t["samples_per_picture"]
+            need = 1.25 * r["bytes_per_sample"] * samples
+            cap = encode.slice_capacity(encode.config(w, h, qp=r["q"], keyint=1, bframes=0, preset="fast"), 2)  # (all-intra: every slice QP is -q)
+            assert cap >= need, (w, h, r["q"], cap, need)
+            if before >= need:
+                assert cap == before, (w, h, r["q"], cap, before)
+                kept.setdefault((w, h), []).append(r["q"])
+    assert 32 in kept[(128, 64)] and 32 in kept[(3840, 2160)] and min(kept[(3840, 2160)]) > 0  # (and the low end is NOT kept: the rule is needed)
+    # the lowest slice QP of the run counts, not -q: the low-delay hierarchy codes its I picture at -q - 1, the 16-picture random-access one at -q - 3 -- where a run has one
+    q0 = encode.slice_capacity(encode.config(128, 64, qp=0, keyint=1, bframes=0, preset="fast"), 2)
+    assert encode.slice_capacity(encode.config(128, 64, qp=1, keyint=0, bframes=0, preset="fast"), 3) == q0 > 5.9 * 1.25 * 128 * 64 * 3 // 2
+    q12 = encode.slice_capacity(encode.config(128, 64, qp=12, keyint=1, bframes=0, preset="fast"), 2)
+    assert encode.slice_capacity(encode.config(128, 64, qp=15, keyint=0, bframes=15, preset="medium"), 17) == q12
+    # and the footprint carries it: per GOP, the slice buffer's growth and nothing else
+    a, b = (encode.config(3840, 2160, qp=q, keyint=8, bframes=15, closed_gop=True, preset="medium", threads=8) for q in (32, 10))
+    grow = encode.slice_capacity(b, 8) - encode.slice_capacity(a, 8)
+    assert grow > 0 and encode.footprint(b, 256, 8)[0] - encode.footprint(a, 256, 8)[0] == 256 * grow  # (256 GOPs: both buffers end on the allocator's 256-byte grain)
+
+
 @pytest.mark.gpu
 def test_gops_coded_in_batches_side_by_side_and_in_rounds_are_the_references(tmp_path):
     import _e2e

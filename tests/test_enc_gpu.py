@@ -116,6 +116,33 @@ def test_p_slices_and_chroma_qp_offsets_on_the_gpu(name, walk, hip, yuv_dir):
     assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in g["per_gop"]]
 
 
+WALK_NAME = {-1: "by_width", 0: "composed", 1: "fused"}  # xeve_hip_walk_select
+
+
+def _qp_range_params():
+    """fast and medium presets on the composed walk AND the fused kernel, slow and placebo on the fused kernel (the only walk that codes them)"""
+    out = []
+    for n in sorted(_enc.QP_RANGE_CASES):
+        fused_only = _enc.QP_RANGE_CASES[n][5][1] in ("slow", "placebo")
+        out += [pytest.param(n, w, id="%s-%s" % (n, WALK_NAME[w])) for w in ((1,) if fused_only else (0, 1))]
+    return out
+
+
+@pytest.mark.parametrize("name,walk", _qp_range_params())
+def test_the_ends_of_the_qp_range_on_the_gpu(name, walk, hip, yuv_dir):
+    """-q 0 .. 2 and 47 .. 51 through the device path -- the walk's quantiser and bit counts at levels in the thousands, the writers with unary level strings thousands of
+    bins long, slice buffers several times the raw picture (sized by the run's lowest slice QP), the QP-1 clamp of a slice of QP 0, the hierarchy's offsets clipped at 51,
+    the chroma tables at both ends, 10-bit input, flat 0 / flat 255 frames: every GOP = the unmodified reference's bytes (tests/golden/enc_v1.json), no harness between"""
+    w, h, gops, frames, seed, cli, threads = _enc.QP_RANGE_CASES[name]
+    g = _enc.golden()["batches"][name]
+    c = _enc.config(w, h, cli, threads)
+    cfg = hip.config(w, h, qp=c.qp, keyint=c.keyint, bframes=c.bframes, closed_gop=c.closed_gop, preset=c.preset, threads=c.threads, ref=c.ref, inter_slice_type=c.inter_slice_type,
+                     qp_cb_offset=c.reserved[2], qp_cr_offset=c.reserved[3], input_depth=c.reserved[1] or 8)
+    with hip.walk_select(walk):
+        outs, _ = _run(hip, cfg, _enc.qp_range_input(yuv_dir, name), frames)
+    assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in g["per_gop"]]
+
+
 @pytest.mark.parametrize("name", sorted(_e2e.SLOW_CASES))
 def test_preset_slow_single_runs_on_the_gpu(name, hip, yuv_dir):
     """--preset slow on the device (the fused walk: walk_dbk.h estimates the loop filter's share of every candidate's distortion -- rdo_dbk_switch = 1 --, the search
@@ -291,7 +318,6 @@ def test_presets_slow_and_placebo_at_1920x1080_on_the_gpu(name, hip, yuv_dir):
 REAL_DEFAULT = {"cfg3_1080p_ra_medium_17f_m8": -1, "cfg2_720p_ldb_fast_8f_m8": 0}  # name -> walk (xeve_hip_walk_select)
 REAL_FULL = {"cfg2_720p_ldb_fast_17f_m8": -1, "cfg2_720p_ldb_fast_64f_m8": 0, "gops_1080p_moving_m8": 0, "cfg3_1080p_ra_medium_9f_m8": 0, "cfg4_2160p_closedgop_medium_2f_m8": -1}
 assert set(REAL_DEFAULT) | set(REAL_FULL) == set(_enc.BATCH_CASES_REAL)
-WALK_NAME = {-1: "by_width", 0: "composed", 1: "fused"}
 
 
 @pytest.mark.gpu_last

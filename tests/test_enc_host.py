@@ -87,6 +87,20 @@ def test_p_slices_and_chroma_qp_offsets_on_the_host_side(name, yuv_dir):
         assert (len(whole), _enc.md5(whole)) == (g["whole"]["bytes"], g["whole"]["md5"])
 
 
+@pytest.mark.parametrize("name", sorted(_enc.QP_RANGE_CASES))
+def test_the_ends_of_the_qp_range_on_the_host_side(name, yuv_dir):
+    """-q 0 .. 2 and 47 .. 51: a slice QP of 0 is quantised at QP 1 (the reference clips the CU's QP to 1 .. 51, xeve_mode.c:753-754) under a header, lambdas and chroma
+    weights of QP 0; the hierarchy's QP offsets clip at 51; the chroma table below index 0 and clipped at 57; presets slow and placebo, 10-bit input, flat 0 / flat 255
+    frames -- every GOP = the unmodified reference's run over it"""
+    w, h, gops, frames, seed, cli, threads = _enc.QP_RANGE_CASES[name]
+    g = _enc.golden()["batches"][name]
+    outs = _enc.encode_cpu(_enc.config(w, h, cli, threads), _enc.qp_range_input(yuv_dir, name), frames)
+    assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in g["per_gop"]]
+    if "whole" in g:
+        whole = b"".join(outs)
+        assert (len(whole), _enc.md5(whole)) == (g["whole"]["bytes"], g["whole"]["md5"])
+
+
 @pytest.mark.parametrize("name", sorted(_e2e.SLOW_CASES))
 def test_preset_slow_single_runs(name, yuv_dir):
     """--preset slow: the search's quarter-pel stage, ME range 128 and rdo_dbk_switch = 1 -- every candidate's distortion includes what the loop filter will do to the CU's

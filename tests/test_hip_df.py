@@ -53,6 +53,25 @@ def test_hip_deblock_vs_oracle(w, h, bd, idc, min_cu):
             assert np.array_equal(got[k], e[k]), (rep, k, np.argwhere(got[k] != e[k])[:4])
 
 
+def test_hip_deblock_over_the_whole_qp_range_vs_oracle():
+    """per-unit QPs 0 .. 51 (the cases above draw 18 .. 51; a slice of QP 0 leaves 0 in the map): the strength table's zero rows, edges between units of QP 0 and 51.  With
+    a Cb offset of -5 the chroma QP of units below 5 is negative: the chroma table is the identity there and the reference indexes its strength table with it -- the row
+    before (oracle/xeve_oracle.c df_st_chroma; held to the reference's bitstreams by the q0_cb-12_cr+12 and q5_cb-12_cr-7_p encodes of tests/_enc.py)"""
+    O = oracle_df()
+    c = make_case(np.random.default_rng(7301), 256, 192, 10, 1, 4, qp_range=(0, 52))
+    c["p"].qp_u_offset, c["p"].qp_v_offset = -5, 3
+    qps = (c["map_scu"] >> 16) & 0x7F
+    assert qps.min() == 0 and qps.max() == 51 and len(np.unique(qps)) > 40
+    e = [p.copy() for p in c["planes"]]
+    ms = c["map_scu"].copy()
+    O.xo_deblock_picture(ptr(e[0], origin(c, 0)), ptr(e[1], origin(c, 1)), ptr(e[2], origin(c, 2)), c["s_l"], c["s_c"], ptr(ms), ptr(c["map_cu_mode"]), ptr(c["refi"]),
+                         ptr(c["mv"]), c["p"])
+    assert any(not np.array_equal(e[k], c["planes"][k]) for k in range(3))  # (the filter did act)
+    got = run_hip(c)
+    for k in range(3):
+        assert np.array_equal(got[k], e[k]), (k, np.argwhere(got[k] != e[k])[:4])
+
+
 @pytest.mark.parametrize("w,h,min_cu,sx,sy", [(256, 128, 8, 2, 0), (320, 200, 4, 3, 2), (1920, 1080, 8, 15, 8)])
 def test_hip_deblock_with_tiles_vs_oracle(w, h, min_cu, sx, sy):
     """edges between units of different tiles stay unfiltered (ctx->map_tidx; the oracle's tile path is pinned to the reference's per-tile loop)"""

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from _libs import SBAC_DTYPE
-from _tree_cases import CASES, CTU_DATA_DTYPE, CTU_JOB_DTYPE, INTER_CASES, make_case, make_inter_case, run_oracle_inter_picture, run_oracle_picture
+from _tree_cases import CASES, CTU_DATA_DTYPE, CTU_JOB_DTYPE, INTER_CASES, QP_EDGE_CASES, make_case, make_inter_case, run_oracle_inter_picture, run_oracle_picture
 
 pytestmark = pytest.mark.gpu
 
@@ -68,6 +68,18 @@ def test_hip_ctu_mode_decision_matches_oracle(case):
     # the walk did decide something: some CTU is split and some CU is kept whole
     depths = np.concatenate([g[0]["depth"].reshape(-1) for g in got])
     assert len(np.unique(depths)) >= 2
+
+
+@pytest.mark.parametrize("case", QP_EDGE_CASES, ids=[str(c[0]) for c in QP_EDGE_CASES])
+def test_hip_ctu_mode_decision_at_the_ends_of_the_qp_range(case):
+    """QP 1 (the quantiser of a slice of QP 0 or 1: quantised levels beyond a thousand through the walk's RDOQ, its bit counts and its reconstruction) and QP 51, 128x64:
+    every CTU's data, coder state and cost as the oracle's"""
+    c = make_case(*case)
+    got, final = run_hip_case(c)
+    compare(case, c, got, final)
+    top = max(int(np.abs(g[0]["coef"].astype(np.int32)).max()) for g in got)
+    print(case, "largest level", top)
+    assert top > 1000 if case[-1] == 1 else 0 < top < 64  # (10-bit texture with noise of +-240 in some tiles: the case does reach the range it is here for)
 
 
 # ---- P / B slices ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -334,6 +346,51 @@ def test_hip_i_pictures_decided_and_written_ctu_by_ctu_on_the_device(case):
     for j in range(3 if c["idc"] else 1):
         assert np.array_equal(mod[j].cpu().numpy(), c["mod"][j]), (case, "picture", j)
     assert np.array_equal(ms.cpu().numpy().view(np.uint32).reshape(m["scu"].shape), m["scu"]) and np.array_equal(mc.cpu().numpy().view(np.uint32).reshape(m["cu_mode"].shape), m["cu_mode"])
+
+
+def test_hip_writer_stores_nothing_beyond_its_capacity_and_still_counts():
+    """what makes a picture that outgrows its slice buffer an error and not a corruption (encode.hip): xeve_hip_eco_ctu_jobs with bytes_cap = half of what the CTU takes,
+    into a destination that keeps its full size and is filled with a sentinel -- every byte from bytes_cap on is still the sentinel, the reported length is the uncapped
+    one, the stored prefix the uncapped prefix (case 3101's first CTU of its first picture, decided on the device)"""
+    import torch
+    import xeve_amd
+    from xeve_amd import device as D
+    from xeve_amd import lib
+
+    c = make_case(*CASES[0])
+    entry = c["entry"][0:1].copy()
+    entry["bitcounter"] = 0
+    xeve_amd.init(0)
+    dev = torch.device("cuda:0")
+    org = [torch.from_numpy(a[0:1].copy()).to(dev) for a in c["org"]]
+    mod = [torch.from_numpy(a[0:1].copy()).to(dev) for a in c["mod"]]
+    m = c["maps"]
+    ms, mi, mt, mc = (torch.from_numpy(m[k][0:1].view(np.int32 if m[k].dtype == np.uint32 else m[k].dtype).copy()).to(dev) for k in ("scu", "ipm", "tidx", "cu_mode"))
+    P = lib.TreeParams.from_buffer_copy(bytes(c["P"]))
+    EP = lib.EcoParams()
+    EP.chroma_format_idc, EP.slice_type, EP.log2_ctu, EP.pic_w, EP.pic_h, EP.w_scu, EP.h_scu = c["idc"], 2, P.log2_ctu, P.pic_w, P.pic_h, P.ip.w_scu, P.ip.h_scu
+    states = torch.from_numpy(entry.view(np.uint8).copy()).to(dev)
+    jobs = np.zeros(1, CTU_JOB_DTYPE)
+    jobs["x"], jobs["y"] = c["order"][0]
+    jt = torch.from_numpy(jobs.view(np.uint8).copy()).to(dev)
+    out, _, _ = D.mode_analyze_ctu_jobs([t.data_ptr() for t in org], org[0].shape[2], org[1].shape[2], [t.data_ptr() for t in mod], mod[0].shape[2], mod[1].shape[2], ms, mi, mt, mc,
+                                        states, P, jt, pic_elems=(org[0][0].numel(), org[1][0].numel(), mod[0][0].numel(), mod[1][0].numel(), m["scu"].shape[1]))
+    FULL, SENTINEL = 1 << 15, 0xA5
+
+    def write(cap):
+        whole = torch.full((FULL,), SENTINEL, dtype=torch.uint8, device=dev)  # (the allocation keeps its size whatever the capacity says)
+        st, scu, cum, nb = states.clone(), ms.clone(), mc.clone(), torch.zeros(1, dtype=torch.int32, device=dev)
+        D.eco_ctu_jobs(out, st, EP, scu, mi, mt, cum, jt, map_pic_elems=m["scu"].shape[1], out=(whole[:cap].view(1, cap), nb))
+        torch.cuda.synchronize()
+        return int(nb.cpu()[0]), whole.cpu().numpy(), st.cpu().numpy()
+
+    full_n, full, full_st = write(FULL)
+    assert 100 < full_n < FULL // 2 and np.all(full[full_n:] == SENTINEL) and not np.all(full[:full_n] == SENTINEL)
+    cap = full_n // 2
+    n, part, st = write(cap)
+    assert np.all(part[cap:] == SENTINEL)
+    assert n == full_n
+    assert np.array_equal(part[:cap], full[:cap]) and np.array_equal(st, full_st)
 
 
 @pytest.mark.parametrize("case", [INTER_CASES[1], INTER_CASES[2]], ids=["4102", "4103"])

@@ -93,6 +93,12 @@ template <bool HOR> __device__ __forceinline__ bool df_is_edge(const unsigned *_
     return !tidx || tidx[t] == tidx[t - 1];
 }
 
+// The strength of a chroma edge.  Below index 0 the chroma QP table is the identity (xeve_util.c:1841-1846), and the reference indexes xeve_tbl_df_st[class] with the
+// negative QP (xeve_df.c:319-321): rows of one array, so classes 1 .. 3 read the tail of the row BEFORE theirs (a "no filtering" edge is filtered with strength 4 .. 10),
+// and class 0 reads in front of the table -- zero padding in the reference build.  Reached with 10-bit pictures and slice QP + chroma offset < 0; reproduced, because
+// the reference's bitstreams are the specification here (tests/_enc.py QP_RANGE_CASES q0_cb-12_cr+12, q5_cb-12_cr-7_p).
+__device__ __forceinline__ int df_st_chroma(int cls, int q) { return q >= 0 ? c_df_st[cls][q] : (cls > 0 ? c_df_st[cls - 1][52 + q] : 0); }
+
 template <bool HOR>
 __global__ __launch_bounds__(256) void k_deblock(pel *__restrict__ y, pel *__restrict__ u, pel *__restrict__ v, const unsigned *__restrict__ map_scu,
                                                  const unsigned *__restrict__ map_cu_mode, const uint8_t *__restrict__ tidx, const int8_t *__restrict__ refi,
@@ -116,7 +122,7 @@ __global__ __launch_bounds__(256) void k_deblock(pel *__restrict__ y, pel *__res
     int cx = sx, cy = sy, ct = t, ccls = cls, cqp = qp;
     for(;;) {
         const int qu = min(57, max(-6 * P.bc, cqp + P.qp_u_offset)), qv = min(57, max(-6 * P.bc, cqp + P.qp_v_offset));
-        const int st_u = c_df_st[ccls][P.qp_chroma[0][qu + 6 * P.bc]] << P.bc, st_v = c_df_st[ccls][P.qp_chroma[1][qv + 6 * P.bc]] << P.bc;
+        const int st_u = df_st_chroma(ccls, P.qp_chroma[0][qu + 6 * P.bc]) << P.bc, st_v = df_st_chroma(ccls, P.qp_chroma[1][qv + 6 * P.bc]) << P.bc;
         const size_t off = (size_t)((4 * cy) >> P.hs) * P.s_c + ((4 * cx) >> P.ws);
         df_segment(u + off, nline, HOR ? 1 : P.s_c, HOR ? P.s_c : 1, st_u, maxc, true);
         df_segment(v + off, nline, HOR ? 1 : P.s_c, HOR ? P.s_c : 1, st_v, maxc, true);
@@ -147,10 +153,10 @@ extern "C" int xeve_hip_deblock(xeve_hip_pel *y, xeve_hip_pel *u, xeve_hip_pel *
     for(int c = 0; c < 2; c++)
         for(int i = 0; i < 100; i++) {
             const int q = p->qp_chroma[c][i];
-            // the mapped chroma QP indexes xeve_tbl_df_st[.][52]; entries below index 6 * (bd - 8) stand for negative QPs, which
-            // the reference would read out of bounds with -- clamp those, insist on the rest
+            // the mapped chroma QP indexes xeve_tbl_df_st[.][52]; entries below index 6 * (bd - 8) stand for negative QPs, which the reference reads
+            // the row before with (df_st_chroma) -- kept negative, within one row; insist on the rest
             XH_REQUIRE(i < 6 * P.bc || i > 57 + 6 * P.bc || (q >= 0 && q < 52));
-            P.qp_chroma[c][i] = q < 0 ? 0 : (q > 51 ? 51 : q);
+            P.qp_chroma[c][i] = q < -52 ? -52 : (q > 51 ? 51 : q);
         }
     const dim3 grid((P.w_scu + 63) / 64, (P.h_scu + 3) / 4);
     hipStream_t st = (hipStream_t)stream;

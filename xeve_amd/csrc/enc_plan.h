@@ -483,6 +483,24 @@ inline int slice_qp(const Param &P, int depth) // xeve_set_sh: the hierarchy's Q
     qp += (int)std::floor(std::min(3.0, std::max(0.0, dqp)));
     return (int)(uint8_t)std::min(51.0, std::max(0.0, qp));
 }
+// The bytes a picture's slice data may take on the device (one buffer per GOP; the writers bounds-check every store, eco_lane.h Sink, and a picture that outgrows it ends
+// the run with an error).  w * h * 3 / 2 + 4096 holds a picture of i.i.d. noise -- the densest content the suite and the benchmark feed -- down to a slice QP of 24 at
+// 3840x2160 (20 at 128x64, where the 4096 bytes count); below, the rate of noise decides: k[q] = the reference's bytes per 256 samples at slice QP q (--preset fast -I 1 -b 0, 128x64, the larger of two pictures:
+// tests/golden/slice_bytes_v1.json, made by tests/golden/make_slice_bytes_golden.py) x 1.25, rounded up and made monotone.  5.97 bytes per sample at QP 0 and 1 (a slice
+// of QP 0 is quantised at QP 1, pic_numbers below).  min_qp: the lowest slice QP of the run (lowest_slice_qp).
+inline int lowest_slice_qp(const Param &P, const std::vector<PicPlan> &plan)
+{
+    int q = 51;
+    for(const PicPlan &pp : plan) q = std::min(q, slice_qp(P, pp.depth));
+    return q;
+}
+inline long slice_capacity(int w, int h, int min_qp)
+{
+    static const uint16_t k[52] = {1911, 1903, 1691, 1530, 1375, 1254, 1126, 1018, 912, 831, 753, 694, 631, 576, 525, 482, 441, 410, 377, 348, 318, 295, 275, 258, 240, 225,
+                                   209,  197,  184,  175,  167,  162,  154,  147,  140, 136, 129, 124, 117, 112, 106, 101, 94,  89,  84,  77,  73,  68,  60,  48,  38,  36};
+    const long samples = (long)w * h * 3 / 2, noise = (samples * k[std::min(51, std::max(0, min_qp))] + 255) / 256;
+    return std::max(samples + 4096, noise);
+}
 struct PicNumbers {
     int    qp, qp_y, qp_u, qp_v;
     double lambda[3], sqrt_lambda0, dcw[2];
@@ -493,7 +511,12 @@ inline PicNumbers pic_numbers(int qp, int qp_u_offset = 0, int qp_v_offset = 0) 
     PicNumbers n;
     const int  off = 6 * (BIT_DEPTH - 8);
     const int  qu = chroma_qp(std::min(57, std::max(-off, qp + qp_u_offset))), qv = chroma_qp(std::min(57, std::max(-off, qp + qp_v_offset)));
-    n.qp = qp, n.qp_y = qp + off, n.qp_u = qu + off, n.qp_v = qv + off;
+    // The quantiser's QPs come from the CU's QP, which get_min_max_qp clips to 1 .. 51 (xeve_mode.c:753-754): a slice of QP 0 is quantised at QP 1.  Its header, its
+    // lambdas and chroma weights (set_lambda with sh->qp, :2406) and the QP field of the unit map (the tile's QP, :914-917: what the loop filter reads) stay at 0.
+    // (walk_dbk.h takes its chroma strengths from qp_u / qp_v: at slice QP 0 that is table entry 1 where the reference's filter reads entry 0 -- xeve_tbl_df_st is 0 below 18.)
+    const int  cu = std::min(51, std::max(1, qp));
+    n.qp = qp, n.qp_y = cu + off;
+    n.qp_u = chroma_qp(std::min(57, std::max(-off, cu + qp_u_offset))) + off, n.qp_v = chroma_qp(std::min(57, std::max(-off, cu + qp_v_offset))) + off;
     n.lambda[0] = 0.57 * std::pow(2.0, (qp - 12.0) / 3.0);
     n.dcw[0] = std::pow(2.0, (qp - qu) / 3.0), n.dcw[1] = std::pow(2.0, (qp - qv) / 3.0);
     n.lambda[1] = n.lambda[0] / n.dcw[0], n.lambda[2] = n.lambda[0] / n.dcw[1];

@@ -263,7 +263,7 @@ struct xeve_hip_enc {
         w_scu = P.w >> 2, h_scu = P.h >> 2, w_lcu = (P.w + CTU - 1) / CTU, h_lcu = (P.h + CTU - 1) / CTU, f_lcu = w_lcu * h_lcu, T = std::min(P.threads, h_lcu);
         vh = (P.h + 2 * PAD_L + 63) & ~63, s_l = P.w + 2 * PAD_L, s_c = P.w / 2 + 2 * PAD_C;
         org_l = (long)vh * P.w, org_c = (long)(vh / 2) * (P.w / 2), pic_l = (long)vh * s_l, pic_c = (long)(vh / 2) * s_c, map_pic = (long)(vh / 4) * w_scu;
-        frame_bytes = P.frame_bytes(), slice_cap = (long)P.w * P.h * 3 / 2 + 4096;
+        frame_bytes = P.frame_bytes();
         if((double)G * org_l >= 8589934592.0) return fail("too many GOPs for one batch at this picture size: the stacked originals must stay below 2^33 samples (xh_common.h: halved 32-bit offsets)");
         if((long)G * T > 65535) return fail("too many GOPs for one batch: GOPs x row chains is a grid dimension (at most 65535)");
         if((double)G * vh * 32 >= 2147483648.0) return fail("too many GOPs for one batch at this picture size: the tall picture's rows in 1/16 sample units must fit 31 bits");
@@ -271,6 +271,7 @@ struct xeve_hip_enc {
         nslots = BatchEncoder<xeve_hip_enc>::slots_needed(P, F);
         if(nslots < 1) return fail("the frame loop needs more picture stores than there are");
         const std::vector<PicPlan> plan = Planner(P, F).run();
+        slice_cap = slice_capacity(P.w, P.h, lowest_slice_qp(P, plan)); // (sized by the run's lowest slice QP: enc_plan.h)
         pos_of_frame.assign(F, -1);
         for(size_t i = 0; i < plan.size(); i++)
             if(plan[i].frame >= 0 && plan[i].frame < F && pos_of_frame[plan[i].frame] < 0) pos_of_frame[plan[i].frame] = (int)i;
@@ -575,6 +576,14 @@ extern "C" int xeve_hip_enc_footprint(const xeve_hip_enc_config *cfg, int ngops,
     const size_t ws = setups.empty() ? 0 : e.workspace_bytes(setups);
     if(ws == 0) { xh_set_error("xeve_hip_enc_footprint: %s", e.error.empty() ? "the frame loop refuses the run" : e.error.c_str()); return XEVE_HIP_ERR_ARG; }
     *device_bytes = (uint64_t)(total + ws);
+    return XEVE_HIP_OK;
+}
+extern "C" int xeve_hip_enc_slice_capacity(const xeve_hip_enc_config *cfg, int frames, uint64_t *bytes)
+{
+    XH_REQUIRE(cfg && frames >= 1 && bytes);
+    Param P;
+    if(!P.finish(*cfg)) { xh_set_error("xeve_hip_enc_slice_capacity: %s", P.error.c_str()); return XEVE_HIP_ERR_ARG; }
+    *bytes = (uint64_t)slice_capacity(P.w, P.h, lowest_slice_qp(P, Planner(P, frames).run()));
     return XEVE_HIP_OK;
 }
 extern "C" int xeve_hip_enc_push(xeve_hip_enc *e, int gop, int frame, const uint8_t *yuv, int on_device)

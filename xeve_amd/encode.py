@@ -134,6 +134,14 @@ def footprint(cfg, ngops, frames):
     return int(b.value), int(m.value)
 
 
+def slice_capacity(cfg, frames):
+    """the bytes one picture's slice data may take on the device, per GOP (sized by the run's lowest slice QP) -- xeve_hip_enc_slice_capacity; no device call"""
+    L = _lib.load()
+    b = C.c_uint64()
+    _lib.check(L.xeve_hip_enc_slice_capacity(C.byref(cfg), int(frames), C.byref(b)))
+    return int(b.value)
+
+
 def plan_batches(cfg, ngops, frames, free_bytes, max_batches=3, reserve_bytes=8 << 30, batch_gops=None):
     """How `ngops` GOPs are cut into batches that run side by side on one GPU (a host thread and a stream each): as few batches as the per-batch limit (32-bit offsets into
     the stacked originals) and the free HBM allow, at most max_batches AT A TIME -- what is left over waits for the next round.  Returns a list of rounds, each a list of
