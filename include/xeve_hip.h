@@ -208,7 +208,8 @@ int xeve_hip_mc_l_jobs(const xeve_hip_pel *ref, int s_ref, xeve_hip_pel *pred, i
 int xeve_hip_mc_c_jobs(const xeve_hip_pel *ref, int s_ref, xeve_hip_pel *pred, int s_pred, const xeve_hip_mc_job *jobs, int njobs,
                        int w, int h, int bit_depth, const int16_t (*coef)[4], void *stream);
 /* Fused forms: the interpolated block is compared with the original at org + jobs[j].pred_off (pred_off is reused as the
- * block's offset inside `org`) and never written.  sad[j] as xeve_mc_l + xeve_sad_16b in me_spel_pattern
+ * block's offset inside `org`, read as an UNSIGNED 32-bit number like xeve_hip_job.off1; with bit 8 of frac set -- the library's own
+ * records -- it counts PAIRS of samples) and never written.  sad[j] as xeve_mc_l + xeve_sad_16b in me_spel_pattern
  * (xeve_pinter.c:593-627); ssd[j] as the MC + xeve_ssd_16b of the skip/merge analysis (xeve_pinter.c:1437-1458).
  * luma: w % 8 == 0; chroma: w % 4 == 0. */
 int xeve_hip_mc_l_sad_jobs(const xeve_hip_pel *ref, int s_ref, const xeve_hip_pel *org, int s_org, const xeve_hip_mc_job *jobs, int njobs,

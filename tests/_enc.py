@@ -157,6 +157,15 @@ BATCH_CASES_REAL = {
     "cfg2_720p_ldb_fast_64f_m8": (1280, 720, 1, 64, 2, ["--preset", "fast", "-b", "0", "-I", "0"], 8),
 }
 
+# A stack that crosses 2^31 and 2^32 samples (GPU: tests/test_enc_batches.py; CPU companion: tests/test_enc_host.py): one CTU row of 1024 samples, closed GOPs of two frames
+# -- the I picture and one inter picture -- on one row chain.  A stacked original is 384 rows x 1024 = 393 216 samples (vh = (64 + 2 * 144 + 63) & ~63), so 2^31 samples lie
+# in GOP 5 461 and 2^32 in GOP 10 922 of a batch; the padded picture stores (stride 1312) cross both earlier.  GOP i of the batch carries clip i % 5 of the ten-frame
+# sequence: five clips whose neighbours and wrap-around targets differ, and no GOP count that is a multiple of 5 divides either boundary.  The golden: one md5 per clip.
+WIDE_STACK_CASES = {
+    "gops_1024x64_moving_5clips": (1024, 64, 5, 2, 5051, ["--preset", "medium", "--closed-gop", "-I", "8"], 1),
+}
+WIDE_STACK_GOPS = 11264  # crosses 2^31 and 2^32 samples of stacked originals and of picture stores
+
 # 10-bit input (the application's -d 10: 16-bit little-endian samples, handed to the codec as they are): the 8-bit clip of the seed widened by widen10
 DEPTH10_CASES = {
     "gops_128x64_10bit_m2": (128, 64, 2, 8, 27, ["--preset", "medium", "--closed-gop", "-I", "8", "-d", "10"], 2),

@@ -109,3 +109,55 @@ def test_gops_coded_in_batches_side_by_side_and_in_rounds_are_the_references(tmp
     out = encode.encode_gops(cfg, N, frames, feed, max_batches=2, batch_gops=4)
     assert fed == [(0, 4), (4, 4), (8, 2)]
     assert [(len(o), _enc.md5(o)) for o in out] == [(gold[i % gops]["bytes"], gold[i % gops]["md5"]) for i in range(N)]
+
+
+def _stack_boundaries(w, h, gops):
+    """GOP indices at which the stacks of a one-chain batch cross 2^31 and 2^32 samples: the stacked originals (vh rows of w samples per GOP) and the padded picture
+    stores (vh rows of w + 2 * 144 samples per GOP)"""
+    vh = (h + 2 * 144 + 63) & ~63
+    out = []
+    for what, per_gop in (("originals", vh * w), ("picture stores", vh * (w + 2 * 144))):
+        for e in (31, 32):
+            if (2 ** e) // per_gop < gops:
+                out.append(("2^%d samples of stacked %s" % (e, what), (2 ** e) // per_gop))
+    return vh, out
+
+
+# (measured on one MI355X: 7.6 s and 98.1 GB of device memory for the 11 264 GOPs; 4.7 s and 49.1 GB for 5 632, which cross 2^31 only -- the whole case is in the default suite)
+@pytest.mark.gpu
+def test_a_batch_whose_stack_crosses_2e31_and_2e32_samples_is_the_references(tmp_path):
+    """one batch of 1024x64 closed GOPs of two frames on one row chain, GOP i = clip i % 5 (tests/_enc.py WIDE_STACK_CASES): every bitstream is the reference application's
+    for its clip -- also those whose pictures lie beyond 2^31 and 2^32 samples of the stack, where the 32-bit job records and every offset a kernel forms are at their
+    limits.  The walk is the library's own choice at this width."""
+    import _e2e
+    import xeve_amd
+
+    xeve_amd.init(0)
+    gops = _enc.WIDE_STACK_GOPS
+    (name, (w, h, clips, frames, seed, cli, threads)), = _enc.WIDE_STACK_CASES.items()
+    gold = _enc.golden()["batches"][name]["per_gop"]
+    vh, bounds = _stack_boundaries(w, h, gops)
+    assert vh == 384 and [g for _, g in bounds] == [5461, 10922, 4262, 8525]
+    assert all((2 ** e) % (vh * w * 5 * k) for e in (31, 32) for k in (1, 2)) and gops % 5  # (no multiple of five GOPs ends on a boundary: the wrap-around target of GOP i is another clip)
+    p = str(tmp_path / "in.yuv")
+    _e2e.make_yuv(p, w, h, clips * frames, seed)
+    data, fb = open(p, "rb").read(), w * h * 3 // 2 * frames
+    c0 = _enc.config(w, h, cli, threads)
+    cfg = encode.config(w, h, qp=c0.qp, keyint=c0.keyint, bframes=c0.bframes, closed_gop=c0.closed_gop, preset=c0.preset, threads=c0.threads, ref=c0.ref)
+    need, most = encode.footprint(cfg, gops, frames)
+    assert most == (2 ** 33 - 1) // (vh * w) == 21845 and gops <= most
+    print("wide stack: %d GOPs, footprint %.1f GB" % (gops, need / 1e9))
+    enc = encode.BatchEncoder(cfg, gops, frames)
+    try:
+        for g in range(gops):
+            enc.push_gop(g, data[(g % clips) * fb:(g % clips + 1) * fb])
+        out = enc.encode()
+    finally:
+        enc.close()
+    want = [(gold[i]["bytes"], gold[i]["md5"]) for i in range(clips)]
+    memo = {}  # (five streams, thousands of copies of each: hash a byte string once)
+    bad = [g for g in range(gops) if memo.setdefault(out[g], (len(out[g]), _enc.md5(out[g]))) != want[g % clips]]
+    if bad:
+        near = lambda g: min(bounds, key=lambda b: abs(b[1] - g))
+        pytest.fail("%d of %d GOPs differ from the reference; the first is GOP %d (nearest boundary: %s, in GOP %d), the last is GOP %d (nearest boundary: %s, in GOP %d); all boundaries: %s"
+                    % (len(bad), gops, bad[0], *near(bad[0]), bad[-1], *near(bad[-1]), bounds))

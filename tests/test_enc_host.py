@@ -59,6 +59,18 @@ def test_batches_of_closed_gops_reproduce_the_reference_run_per_gop(name, yuv_di
     assert (len(whole), _enc.md5(whole)) == (g["whole"]["bytes"], g["whole"]["md5"])
 
 
+@pytest.mark.parametrize("name", sorted(_enc.WIDE_STACK_CASES))
+def test_the_clips_of_the_wide_stack_reproduce_the_reference_runs(name, yuv_dir):
+    """1024x64, five closed GOPs of two frames: the picture geometry of the batch that tests/test_enc_batches.py stacks past 2^32 samples on the GPU, against the same
+    goldens -- a wrong picture geometry fails here first"""
+    w, h, gops, frames, seed, cli, threads = _enc.WIDE_STACK_CASES[name]
+    g = _enc.golden()["batches"][name]
+    data, fb = _frames(yuv_dir, name, w, h, gops * frames, seed), w * h * 3 // 2 * frames
+    outs = _enc.encode_cpu(_enc.config(w, h, cli, threads), [data[i * fb:(i + 1) * fb] for i in range(gops)], frames)
+    assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in g["per_gop"]]
+    assert len({p["md5"] for p in g["per_gop"]}) == gops  # (five DIFFERENT streams: a GOP that reads a neighbour's or a wrap-around target's samples shows)
+
+
 @pytest.mark.parametrize("name", sorted(_enc.DEPTH10_CASES))
 def test_ten_bit_input_is_handed_to_the_codec_as_it_is(name, yuv_dir):
     """the application's -d 10: 16-bit samples, no conversion -- every GOP = the reference's run over it, and the concatenation = its one run over the sequence"""

@@ -380,3 +380,291 @@ def test_fused_mc_distortion_vs_oracle(dev, luma):
             assert ssd[i] == O.xo_ssd(w, h, ptr(org, ooff[i]), ptr(e), s, w, 10), (luma, w, i)
             if luma:
                 assert sad[i] == O.xo_sad(w, h, ptr(org, ooff[i]), ptr(e), s, w, 10), (w, i)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# far offsets: every kernel that decodes a job record (xh_common.h xh_job / xh_pred_off), at blocks of plane 1 that
+# lie 2^31, 2^32 and almost 2^33 samples in -- where the stacked originals of a real batch are (tests/test_job_records.py
+# holds the decode itself to its domain on the CPU)
+# ---------------------------------------------------------------------------------------------------------
+FAR_GUARD = 2 ** 31  # samples in front of plane 1: a sign-extended off1 lands here, inside the allocation -- a mismatch, not a fault
+FAR_SPAN = 2 ** 33   # what the halved records address
+FAR_TAIL = 1 << 16   # behind it: room for the window the residual tests watch behind the last block
+FAR_S1 = 1312        # stride of plane 1: the padded 1024-wide picture's
+HALF2, HALFF = 1 << 30, 1 << 8  # XH_OFF2_HALF, XH_FRAC_HALF
+
+
+class FarPlane:
+    """an int16 buffer of 2^31 + 2^33 samples that nothing fills; positions are samples relative to p1 = base + 2^31"""
+
+    def __init__(self, dev):
+        import torch
+
+        self.dev = dev
+        self.base = torch.empty(FAR_GUARD + FAR_SPAN + FAR_TAIL, dtype=torch.int16, device=dev)
+        self.p1 = self.base[FAR_GUARD:]
+
+    def inside(self, pos, w, h):
+        return pos >= -FAR_GUARD and pos + (h - 1) * FAR_S1 + w <= FAR_SPAN
+
+    def put(self, pos, blk):
+        import torch
+
+        h, w = blk.shape
+        self.base.as_strided((h, w), (FAR_S1, 1), FAR_GUARD + pos).copy_(torch.from_numpy(np.ascontiguousarray(blk)).to(self.dev))
+
+    def get(self, pos, w, h):
+        return self.base.as_strided((h, w), (FAR_S1, 1), FAR_GUARD + pos).cpu().numpy().copy()
+
+    def put_flat(self, pos, a):
+        import torch
+
+        self.base[FAR_GUARD + pos:FAR_GUARD + pos + len(a)].copy_(torch.from_numpy(a).to(self.dev))
+
+    def get_flat(self, pos, n):
+        return self.base[FAR_GUARD + pos:FAR_GUARD + pos + n].cpu().numpy().copy()
+
+    def free(self):
+        self.base = self.p1 = None
+
+
+def _far_fixture(dev):
+    import torch
+
+    f = FarPlane(dev)
+    yield f
+    f.free()
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()  # (the 4K encodes at the end of the suite need the memory)
+
+
+@pytest.fixture(scope="module")
+def far(dev):
+    yield from _far_fixture(dev)
+
+
+@pytest.fixture(scope="module")
+def far_rec(dev):
+    """the reconstruction's plane of the residual chains: off1 addresses both, so it has the original's geometry"""
+    yield from _far_fixture(dev)
+
+
+def far_probes(w, h):
+    """block positions (plain records, records marked as the library marks them); block extent = (h - 1) * s1 + w"""
+    ext = (h - 1) * FAR_S1 + w
+    return [(2 ** 31 - ext) & ~1, 2 ** 31 + 6, 2 ** 32 - ext - 1], [2 ** 31 + 8, 2 ** 32 + 8, (2 ** 33 - ext) & ~1]
+
+
+def far_aliases(P):
+    """where a wrong decode of the record for P reads: sign extension (P mod 2^32, P - 2^32; of a halved off1: P - 2^33), the doubling forgotten (P / 2), an unmarked
+    record doubled (2P mod 2^33), an offset kept in 31 bits (P mod 2^31)"""
+    return sorted({P % 2 ** 32, P - 2 ** 32, P - 2 ** 33, P // 2, (2 * P) % 2 ** 33, P % 2 ** 31} - {P})
+
+
+def far_setup(plane, r, w, h, lo=0, hi=1024):
+    """seeded blocks at every probe and OTHER seeded blocks at each of its aliases that lies inside the allocation; returns the probes and what the plane holds there
+    (blocks that overlap end as the later write left them, so the reference reads them back)"""
+    plain, marked = far_probes(w, h)
+    assert plain[2] % 2 == 1 and all(p % 2 == 0 for p in marked) and all(plane.inside(p, w, h) for p in plain + marked)
+    for P in plain + marked:
+        for A in far_aliases(P):
+            if plane.inside(A, w, h):
+                plane.put(A, r.integers(lo, hi, size=(h, w), dtype=np.int16))
+    for P in plain + marked:
+        plane.put(P, r.integers(lo, hi, size=(h, w), dtype=np.int16))
+    blocks = {P: plane.get(P, w, h) for P in plain + marked}
+    n_alias = 0
+    for P in plain + marked:
+        for A in far_aliases(P):
+            if plane.inside(A, w, h):
+                assert not np.array_equal(plane.get(A, w, h), blocks[P]), (P, A)  # a wrong decode reads OTHER data
+                n_alias += 1
+    assert n_alias >= 12
+    return plain, marked, blocks
+
+
+def far_records(plain, marked, off2s):
+    """one record per (probe, off2): (off1, off2) as the uint32 / int32 words, and the probe each belongs to"""
+    rec1, rec2, where = [], [], []
+    for k, P in enumerate(plain + marked):
+        for o2 in off2s[k]:
+            half = P in marked
+            assert not half or o2 >= 0
+            rec1.append(P // 2 if half else P), rec2.append(o2 | HALF2 if half else o2), where.append(P)
+    assert max(rec1) >= 2 ** 31
+    return rec1, rec2, where
+
+
+FAR_SIZES = [(4, 4), (8, 8), (16, 16), (32, 32), (64, 64), (128, 64), (16, 8), (4, 8), (8, 32)]  # one per path of sad.hip's dispatch: tiny, the four squares, any + SATD tiles 8x8 / 16x8 / 4x8 / 8x16
+
+
+@pytest.mark.parametrize("w,h", FAR_SIZES)
+def test_distortions_at_far_offsets_vs_oracle(dev, far, w, h):
+    import torch
+
+    from xeve_amd import device as D
+
+    r = np.random.default_rng(900 + w * 7 + h)
+    O = oracle()
+    bd, pad, s2 = 10, 24, 320
+    ref = r.integers(0, 1 << bd, size=(64 + 2 * pad + 16, s2), dtype=np.int16)
+    mid = (pad + 8) * s2 + pad + 8  # plane 2 is handed over from here: a caller's record may carry a negative off2
+    d_ref = torch.from_numpy(ref).to(dev).view(-1)
+    d_p2 = d_ref[mid:]
+    assert d_p2.data_ptr() % 4 == 0
+    d_sh = D.plane_shift1(d_ref)[mid:]
+    few = np.array([0, 1, -1, s2, -s2, 3 * s2 + 2], np.int32)
+    many = diamond(s2)[0][:33]  # (>= 32 candidates: the split form of the square SAD kernels)
+    assert np.abs(many).max() <= 8 * s2 + 8
+    for signed in (False, True):
+        plain, marked, blocks = far_setup(far, r, w, h, *((-1023, 2047) if signed else (0, 1024)))
+        off2s = [[int(r.integers(0, 16)) * s2 + int(r.integers(0, 64)) for _ in range(3)] for _ in range(6)]
+        for k in range(3):
+            off2s[k][0] = -int(r.integers(1, 8)) * s2 - int(r.integers(0, 8))  # (plain records only: bit 31 set, never taken for the mark)
+        rec1, rec2, where = far_records(plain, marked, off2s)
+        jobs = D.make_jobs(rec1, rec2, dev)
+        o2 = [x & (HALF2 - 1) if P in marked else x for x, P in zip(rec2, where)]
+        got = {}
+        for name, cand in (("few", few), ("many", many)):
+            d_cand = torch.from_numpy(cand).to(dev)
+            got["sad", name] = D.sad_jobs(far.p1, FAR_S1, d_p2, s2, jobs, d_cand, w, h, bd, signed=signed).cpu().numpy()
+            got["dual", name] = D.sad_jobs_dual(far.p1, FAR_S1, d_p2, d_sh, s2, jobs, d_cand, w, h, bd, signed=signed).cpu().numpy()
+        if not signed:
+            d_cand = torch.from_numpy(few).to(dev)
+            got["ssd"] = D.ssd_jobs(far.p1, FAR_S1, d_p2, s2, jobs, d_cand, w, h, bd).cpu().numpy()
+            got["satd"] = D.satd_jobs(far.p1, FAR_S1, d_p2, s2, jobs, d_cand, w, h, bd).cpu().numpy()
+            got["diff"] = D.diff_jobs(far.p1, FAR_S1, d_p2, s2, jobs, w, h).cpu().numpy()
+        for j, P in enumerate(where):
+            a = ptr(blocks[P])
+            for name, cand in (("few", few), ("many", many)):
+                exp = [O.xo_sad(w, h, a, ptr(ref, mid + o2[j] + int(c)), w, s2, bd) for c in cand]
+                assert list(got["sad", name][j]) == exp, ("sad", signed, name, P, j)
+                assert list(got["dual", name][j]) == exp, ("dual", signed, name, P, j)
+            if not signed:
+                assert list(got["ssd"][j]) == [O.xo_ssd(w, h, a, ptr(ref, mid + o2[j] + int(c)), w, s2, bd) for c in few], ("ssd", P, j)
+                assert list(got["satd"][j]) == [O.xo_satd(w, h, a, ptr(ref, mid + o2[j] + int(c)), w, s2, bd) for c in few], ("satd", P, j)
+                e = np.zeros((h, w), np.int16)
+                O.xo_diff(w, h, a, ptr(ref, mid + o2[j]), w, s2, w, ptr(e))
+                assert np.array_equal(got["diff"][j], e), ("diff", P, j)
+
+
+def _chain_expect(O, blk, pred, lw, lh, bd, qp, intra, quantise):
+    """the oracle's step-by-step residual chain of one block: levels, their count, the reconstruction and both SSDs"""
+    w, h = 1 << lw, 1 << lh
+    dqs = _DQ_SCALE[qp % 6] << (qp // 6)
+    c = np.zeros(w * h, np.int16)
+    O.xo_diff(w, h, ptr(blk), ptr(pred), w, w, w, ptr(c))
+    ssd0 = O.xo_ssd(w, h, ptr(blk), ptr(pred), w, w, bd)
+    O.xo_trans(ptr(c), lw, lh, bd)
+    nnz = quantise(c)
+    lev = c.copy()
+    O.xo_dquant(ptr(c), lw, lh, dqs, bd)
+    O.xo_itrans(ptr(c), lw, lh, bd)
+    e = np.zeros((h, w), np.int16)
+    O.xo_recon(ptr(c), ptr(pred), 1, w, h, w, ptr(e), bd)
+    return lev, nnz, e, ssd0, O.xo_ssd(w, h, ptr(blk), ptr(e), w, w, bd)
+
+
+_DQ_SCALE = (40, 45, 51, 57, 64, 71)
+
+
+@pytest.mark.parametrize("rdoq", [False, True])
+@pytest.mark.parametrize("lw,lh", [(3, 3), (5, 5), (6, 6)])  # tq.hip's chain; dct_mfma.hip's at 32x32 and at 64x64
+def test_residual_chains_at_far_offsets_vs_oracle(dev, far, far_rec, lw, lh, rdoq):
+    """off1 addresses the original AND the reconstruction: the reconstructed block lands at the far position of a second plane of the same geometry, and not one sample
+    around it -- a stride and 16 samples before the block to a stride and 16 behind it -- nor at any alias of the position changes"""
+    import ctypes as C
+
+    import torch
+
+    from _libs import oracle_rdoq
+    from _rdoq_cases import make_est
+    from xeve_amd import device as D
+    from xeve_amd import lib
+
+    r = np.random.default_rng(1000 + lw * 8 + lh + 64 * rdoq)
+    O, OR = oracle(), oracle_rdoq()
+    w, h, bd, n = 1 << lw, 1 << lh, 10, 1 << (lw + lh)
+    ext = (h - 1) * FAR_S1 + w
+    plain, marked, blocks = far_setup(far, r, w, h)
+    qp, intra, lam, luma = (27, 0, 38.5, 1) if rdoq else (32, 1, 0.0, 1)
+    qs = D.QUANT_SCALE[0][qp % 6]
+    est = make_est(r) if rdoq else None
+
+    def quantise(c):
+        if not O.xo_rdoq_zero_test(ptr(c), lw, lh, qp, qs, intra, bd):
+            c[:] = 0
+            return 0
+        return OR.xo_rdoq(ptr(c), lw, lh, qp, lam, luma, bd, 0, C.byref(est)) if rdoq else O.xo_quant(ptr(c), lw, lh, qp, qs, intra, bd)
+
+    coded = 0
+    for probes, half in ((plain, False), (marked, True)):  # (a launch each: the blocks at 2^31 + 6 and 2^31 + 8 overlap)
+        # predictions: a near-perfect one (the zero pre-test and small levels), a fair one, and one that has nothing to do with the block (large levels)
+        pred = np.stack([np.clip(blocks[P] + r.integers(-40 * k - 2, 40 * k + 3, size=(h, w)), 0, 1023).astype(np.int16).reshape(-1) for k, P in enumerate(probes)])
+        pred[2] = r.integers(0, 1024, size=n, dtype=np.int16)
+        jobs = D.make_jobs([P // 2 if half else P for P in probes], [k * n | (HALF2 if half else 0) for k in range(3)], dev)
+        # what is watched in the reconstruction's plane: a window around every block and every alias block inside the allocation
+        windows = [(P - FAR_S1 - 16, ext + 2 * FAR_S1 + 32) for P in probes]
+        windows += [(A, ext) for P in probes for A in far_aliases(P) if far_rec.inside(A, w, h)]
+        for start, length in windows:
+            far_rec.put_flat(start, r.integers(-3000, -2000, size=length, dtype=np.int16))
+        before = [far_rec.get_flat(start, length) for start, length in windows]
+        coef = torch.full((3, n), 77, dtype=torch.int16, device=dev)
+        nnz = torch.zeros(3, dtype=torch.int32, device=dev)
+        ssd = torch.zeros((3, 2), dtype=torch.int64, device=dev)
+        d_pred = torch.from_numpy(pred).to(dev)
+        if rdoq:
+            D.residual_rdoq(far.p1, FAR_S1, d_pred, w, jobs, lw, lh, bd, qp, intra, lam, luma, lib.RdoqEst.from_buffer_copy(bytes(est)), coef, far_rec.p1, FAR_S1, nnz, ssd)
+        else:
+            D.residual_rdo(far.p1, FAR_S1, d_pred, w, jobs, lw, lh, bd, qp, intra, 1, coef, far_rec.p1, FAR_S1, nnz, ssd)
+        coef, nnz, ssd = coef.cpu().numpy(), nnz.cpu().numpy(), ssd.cpu().numpy()
+        recs = {}
+        for k, P in enumerate(probes):
+            lev, e_nnz, e, ssd0, ssd1 = _chain_expect(O, blocks[P], pred[k], lw, lh, bd, qp, intra, quantise)
+            assert nnz[k] == e_nnz and np.array_equal(coef[k], lev), ("levels", half, P)
+            assert (ssd[k, 0], ssd[k, 1]) == (ssd0, ssd1), ("ssd", half, P)
+            assert np.array_equal(far_rec.get(P, w, h), e), ("rec", half, P)
+            recs[P] = e
+            coded += e_nnz
+        idx = (np.arange(h)[:, None] * FAR_S1 + np.arange(w)[None, :]).ravel()
+        for (start, length), b in zip(windows, before):
+            exp = b.copy()
+            for P in probes:
+                at = P + idx - start
+                ok = (at >= 0) & (at < length)
+                exp[at[ok]] = recs[P].ravel()[ok]
+            assert np.array_equal(far_rec.get_flat(start, length), exp), ("around", half, start)
+    assert coded > 0
+
+
+@pytest.mark.parametrize("luma", [True, False])
+def test_fused_mc_distortion_at_far_offsets_vs_oracle(dev, far, luma):
+    """pred_off, the block's offset in the original, in its plain form (unsigned) and in the halved form the sub-pel search builds (frac | XH_FRAC_HALF)"""
+    import torch
+
+    from xeve_amd import device as D
+
+    r = np.random.default_rng(1100 + luma)
+    O = oracle()
+    pad, W, H = 72, 192, 128
+    s = W + 2 * pad
+    ref = r.integers(0, 1024, size=(H + 2 * pad, s), dtype=np.int16)
+    d_ref = torch.from_numpy(ref).to(dev)
+    unit = 16 if luma else 32
+    for (w, h) in ([(8, 8), (16, 16), (32, 32), (64, 64)] if luma else [(4, 4), (8, 8), (16, 16), (32, 32)]):
+        plain, marked, blocks = far_setup(far, r, w, h)
+        where = [P for P in plain + marked for _ in range(4)]
+        n = len(where)
+        gx = [(pad + int(r.integers(-30, W + 30 - w))) * unit + (int(r.integers(1, unit // 4)) * 4 if i & 1 else 0) for i in range(n)]  # (the four filters at every probe)
+        gy = [(pad + int(r.integers(-30, H + 30 - h))) * unit + (int(r.integers(1, unit // 4)) * 4 if i & 2 else 0) for i in range(n)]
+        frac = [int((x & (unit - 1)) != 0) | (int((y & (unit - 1)) != 0) << 1) for x, y in zip(gx, gy)]
+        assert frac == [i & 3 for i in range(n)]
+        jobs = D.make_mc_jobs(gx, gy, [P // 2 if P in marked else P for P in where], [f | (HALFF if P in marked else 0) for f, P in zip(frac, where)], dev)
+        ssd = D.mc_ssd_jobs(luma, d_ref, s, far.p1, FAR_S1, jobs, w, h, 10, torch.zeros(n, dtype=torch.int64, device=dev)).cpu().numpy()
+        sad = D.mc_l_sad_jobs(d_ref, s, far.p1, FAR_S1, jobs, w, h, 10, torch.zeros(n, dtype=torch.int32, device=dev)).cpu().numpy() if luma else None
+        for i, P in enumerate(where):
+            e = np.zeros((h, w), np.int16)
+            (O.xo_mc_l if luma else O.xo_mc_c)(frac[i] & 1, frac[i] >> 1, ptr(ref), gx[i], gy[i], s, w, ptr(e), w, h, 10, O.mc_l_coeff if luma else O.mc_c_coeff)
+            assert ssd[i] == O.xo_ssd(w, h, ptr(blocks[P]), ptr(e), w, w, 10), (luma, w, P, i)
+            if luma:
+                assert sad[i] == O.xo_sad(w, h, ptr(blocks[P]), ptr(e), w, w, 10), (w, P, i)

@@ -498,6 +498,7 @@ int xh_pinter_analyze_cu_jobs_x(const xeve_hip_pel *const org[3], int s_org_l, i
     const xeve_hip_rdo_params rp = p->rdo;
     const int idc = rp.chroma_format_idc, ws = idc <= 2, hs = idc <= 1, bd = rp.bit_depth, lw = rp.log2_cuw, w = 1 << lw;
     XH_REQUIRE(org[0] && (idc == 0 || (org[1] && org[2] && coef_c && rec_u && rec_v)));
+    XH_REQUIRE(xh_dense_ok(njobs, (long)w * w)); // (the winners' records carry j * n0 as off2: xh_common.h XH_OFF2_HALF)
     const InterLayout L = inter_layout(njobs, nstates, p, s_org_l, s_org_c);
     XH_REQUIRE(workspace_bytes >= L.total);
     InterK P;

@@ -339,6 +339,7 @@ int xh_pintra_analyze_cu_jobs_x(const xeve_hip_pel *const org[3], int s_org_l, i
     XH_REQUIRE(intra_params_ok(p));
     XH_REQUIRE(org[0] && mod[0] && (p->chroma_format_idc == 0 || (org[1] && org[2] && mod[1] && mod[2])));
     if(njobs == 0) return XEVE_HIP_OK;
+    XH_REQUIRE(xh_dense_ok((long)njobs * SLOTS, 1L << (2 * p->log2_cuw))); // (the slots' records carry t * n0 as off2: xh_common.h XH_OFF2_HALF)
     XH_REQUIRE(workspace_bytes >= xeve_hip_pintra_analyze_cu_workspace(njobs, nstates, p));
     const int idc = p->chroma_format_idc, ws = idc <= 2, hs = idc <= 1, bd = p->bit_depth, lw = p->log2_cuw;
     IntraK P;

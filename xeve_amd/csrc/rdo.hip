@@ -424,6 +424,7 @@ int xh_residue_rdo_jobs_x(const xeve_hip_pel *const org[3], int s_org_l, int s_o
     XH_REQUIRE(p->chroma_format_idc == 0 || p->chroma_format_idc == 1 || p->chroma_format_idc == 3);
     XH_REQUIRE(org[0] && (p->chroma_format_idc == 0 || (org[1] && org[2] && coef_c)));
     if(njobs == 0) return XEVE_HIP_OK;
+    XH_REQUIRE(xh_dense_ok(njobs, 1L << (p->log2_cuw + p->log2_cuh))); // (the chains' records carry j * n0 as off2: xh_common.h XH_OFF2_HALF)
     XH_REQUIRE(workspace_bytes >= xeve_hip_residue_rdo_workspace(njobs, nstates, p, s_org_l, s_org_c));
     const int idc = p->chroma_format_idc, ws = idc <= 2, hs = idc <= 1, bd = p->bit_depth;
     const int lw[3] = {p->log2_cuw, p->log2_cuw - ws, p->log2_cuw - ws}, lh[3] = {p->log2_cuh, p->log2_cuh - hs, p->log2_cuh - hs};
@@ -660,6 +661,7 @@ extern "C" int xeve_hip_analyze_skip_jobs(const xeve_hip_pel *const org[3], int 
     SkipK P;
     P.njobs = njobs, P.mc = max_cand, P.isb = p->slice_type == 0, P.S = skip_slots(p, max_cand);
     XH_REQUIRE((long)njobs * P.S < (1L << 30) / 64);
+    XH_REQUIRE(xh_dense_ok((long)njobs * P.S, 1L << (p->log2_cuw + p->log2_cuh))); // (t * n0 as off2: xh_common.h XH_OFF2_HALF)
     P.n0 = 1 << (p->log2_cuw + p->log2_cuh), P.n1 = idc ? P.n0 >> (ws + hs) : 0, P.ncomp = idc ? 3 : 1, P.ws = ws, P.hs = hs;
     P.s_org_l = s_org_l, P.s_org_c = s_org_c, P.best_shift = p->log2_cuw + p->log2_cuh + 16; // pi->best_ssd's reset value
     P.lambda0 = p->lambda[0], P.wgt[0] = p->dist_chroma_weight[0], P.wgt[1] = p->dist_chroma_weight[1];

@@ -817,6 +817,7 @@ extern "C" int xeve_hip_mode_analyze_ctu_jobs(const xeve_hip_pel *const org[3], 
         (void)ws_;
     }
     if(nchains == 0) return XEVE_HIP_OK;
+    XH_REQUIRE(xh_dense_ok(nchains, 1L << (2 * p->log2_ctu))); // (op_enter's records carry c * cu * cu as off2: xh_common.h XH_OFF2_HALF)
     // which walk: by the WIDTH OF THE BATCH the call belongs to (the caller's state records: every chain of every GOP), not by the chains this step carries -- the ramp
     // steps of a wide batch's pictures stay on the composed walk (a long-running fused launch between the other streams' short kernels cost 7 %, profiles/r04_walks.md)
     // rdo_dbk_switch and 4x4 inter CUs (presets slow, placebo) live in the fused walk alone (walk_dbk.h, walk_inter.h): the composed walk's stages do neither

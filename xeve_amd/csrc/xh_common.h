@@ -134,10 +134,20 @@ __host__ __device__ __forceinline__ int xh_vh_base(int y, int vh) { return vh > 
 // Offsets into the ORIGINAL (xeve_hip_job.off1, the fused comparison's pred_off) are 32-bit element counts read as UNSIGNED: 2^32 samples = 448 stacked pictures of
 // 3840x2160.  The job lists the library builds ITSELF go further: every offset it produces is EVEN (CUs start on multiples of 4 luma / 2 chroma samples, strides and
 // picture distances are multiples of 4), so it travels HALVED -- 2^33 samples, 896 pictures of 3840x2160, all a GPU's HBM holds in ONE batch -- and says so in the record:
-// bit 30 of off2 (XH_OFF2_HALF; the dense second operand's offsets stay far below it) resp. bit 8 of an interpolation job's frac (XH_FRAC_HALF).  A caller's own records
-// (any offset, odd ones too) carry no mark and mean what include/xeve_hip.h says.  Consumers decode a record once (xh_job) and use the decoded fields.
+// bit 30 of off2 (XH_OFF2_HALF) resp. bit 8 of an interpolation job's frac (XH_FRAC_HALF).  A caller's own records (any offset, odd ones too) carry no mark and mean
+// what include/xeve_hip.h says.  Consumers decode a record once (xh_job / xh_pred_off) and use the decoded fields.
+// THE DOMAIN of the records (tests/native/job_record_host.cpp walks its edges on the host):
+//   a caller's record      off1 = any of 0 .. 2^32 - 1, off2 = INT_MIN + 1 .. 2^30 - 1                                  decodes to itself
+//   xh_make_job(o, off2)   off2 = INT_MIN + 1 .. 2^30 - 1;  o even: below 2^33 where off2 >= 0 (halved and marked), below 2^32 where off2 < 0 (bit 31 of off2 is the
+//                          sign, a mark there could not be told from it);  o odd: below 2^32 (stays as it is)          xh_job(xh_make_job(o, off2)) == (o, off2)
+//   xh_make_pred_off(o)    o even: below 2^33 (halved and marked);  o odd: below 2^32                                   xh_pred_off(xh_make_pred_off(o)) == o
+// Bit 30 of a non-negative off2 IS the mark, so an off2 of 2^30 .. 2^31 - 1 cannot travel in any record: the dense second operand stays below 2^30 elements, which the
+// host entry points that size it require (xh_dense_ok).  Outside the domain the makers produce no record that decodes to another block: xh_make_job returns
+// XH_JOB_NONE = (0xFFFFFFFF, INT_MIN) -- INT_MIN is no off2 of the domain, so no record made from inside it looks like this one -- and xh_make_pred_off a job that is
+// switched off (frac bit 2).  The stacked originals stay below 2^33 samples through xeve_hip_enc_footprint.
 #define XH_OFF2_HALF 0x40000000
 #define XH_FRAC_HALF 0x100
+#define XH_FRAC_OFF 4 // the interpolation job is switched off (xeve_hip_mc_cu_jobs)
 // what only the fused CTU walk (walk.hip) codes: rdo_dbk_switch (the loop filter's share of the distortions, walk_dbk.h) and inter CUs of 4x4 (min_cu_inter 4) --
 // presets slow and placebo.  The composed walk's stage kernels cover square inter CUs of 8 .. 64 without the filter estimate.
 inline bool xh_walk_only(const xeve_hip_tree_params *p) { return p->rdo_dbk != 0 || (p->ip.slice_type != 2 && p->min_cu < 8); }
@@ -156,15 +166,36 @@ __host__ __device__ __forceinline__ XhJob xh_job(const xeve_hip_job &j)
 __host__ __device__ __forceinline__ size_t xh_u(size_t off) { return off; } // (a decoded record's offset)
 __host__ __device__ __forceinline__ size_t xh_u(int off) { return (size_t)(uint32_t)off; }
 // a job record of the library's own making for the block at element offset o of plane 1: halved and marked when o is even (always, for the encoder's pictures); an odd
-// offset (a C-ABI caller's CU at an odd position or with an odd stride) stays as it is, below 2^32
+// offset (a C-ABI caller's CU at an odd position or with an odd stride) or one that goes with a negative off2 stays as it is, below 2^32
+__host__ __device__ __forceinline__ bool xh_job_ok(size_t o, int off2)
+{
+    if(off2 == INT32_MIN || off2 >= XH_OFF2_HALF) return false;
+    return o < ((o & 1) || off2 < 0 ? (size_t)1 << 32 : (size_t)1 << 33);
+}
 __host__ __device__ __forceinline__ xeve_hip_job xh_make_job(size_t o, int off2)
 {
     xeve_hip_job j;
-    // (the halved form keeps bit 30 of off2 for its mark: an off2 outside 0 .. 2^30 - 1 -- a dense offset beyond a gigasample, ADVICE r05 -- stays unhalved)
-    if((o & 1) || off2 < 0 || off2 >= XH_OFF2_HALF) j.off1 = (int)(uint32_t)o, j.off2 = off2;
+    if(!xh_job_ok(o, off2)) j.off1 = -1, j.off2 = INT32_MIN; // XH_JOB_NONE
+    else if((o & 1) || off2 < 0) j.off1 = (int)(uint32_t)o, j.off2 = off2;
     else j.off1 = (int)(uint32_t)(o >> 1), j.off2 = off2 | XH_OFF2_HALF;
     return j;
 }
+// the dense second operand of a launch's own records -- njobs blocks of n elements, block t at t * n -- stays below the mark: what the host entry points require of
+// the buffers they size (rdo.hip, inter.hip, intra.hip, tree.hip)
+__host__ __device__ __forceinline__ bool xh_dense_ok(long nblocks, long n) { return nblocks >= 0 && n >= 0 && (n == 0 || nblocks <= ((long)XH_OFF2_HALF - 1) / n); } // nblocks * n < 2^30
+// the same pair for the fused comparison's pred_off (mc.hip: k_spel_make builds, k_mc_fir reads): the block at element offset o of the original
+struct XhPredOff {
+    int pred_off, frac; // frac: the bits to OR into the job's frac
+};
+__host__ __device__ __forceinline__ XhPredOff xh_make_pred_off(size_t o)
+{
+    XhPredOff r;
+    if(o & 1) r.pred_off = (int)(uint32_t)o, r.frac = o < ((size_t)1 << 32) ? 0 : XH_FRAC_OFF;
+    else r.pred_off = (int)(uint32_t)(o >> 1), r.frac = o < ((size_t)1 << 33) ? XH_FRAC_HALF : XH_FRAC_OFF;
+    if(r.frac == XH_FRAC_OFF) r.pred_off = 0;
+    return r;
+}
+__host__ __device__ __forceinline__ size_t xh_pred_off(int pred_off, int frac) { return (frac & XH_FRAC_HALF) ? (size_t)(uint32_t)pred_off << 1 : xh_u(pred_off); }
 __host__ __device__ __forceinline__ xeve_hip_job xh_make_job(long y, long stride, long x, int off2) { return xh_make_job((size_t)(y * stride + x), off2); }
 __device__ __forceinline__ int xh_plane_of_job(const unsigned char *job_plane, int per_plane, int j) { return job_plane ? job_plane[j] : j / per_plane; }
 // the encoder's per-unit maps a CU's merge / MVP candidates are derived from (xeve_hip_inter_candidates' arguments; inter.hip)

@@ -30,14 +30,25 @@ def _i16(t):
     return t
 
 
+def _i32(a):
+    """the int32 words of a record field given as signed values or as unsigned ones up to 2^32 - 1 (xeve_hip_job.off1 and the fused comparison's pred_off are read
+    as unsigned: include/xeve_hip.h)"""
+    a = np.asarray(a)
+    if a.dtype == np.int32:
+        return a
+    a = a.astype(np.int64)
+    assert a.size == 0 or (-2 ** 31 <= int(a.min()) and int(a.max()) < 2 ** 32), "a record field holds 32 bits"
+    return a.astype(np.uint32).view(np.int32)
+
+
 def make_jobs(off1, off2, device):
     """xeve_hip_job[n] as an int32 [n, 2] device tensor."""
-    j = np.stack([np.asarray(off1, np.int32), np.asarray(off2, np.int32)], axis=1)
+    j = np.stack([_i32(off1), _i32(off2)], axis=1)
     return torch.from_numpy(np.ascontiguousarray(j)).to(device)
 
 
 def make_mc_jobs(gmv_x, gmv_y, pred_off, frac, device):
-    j = np.stack([np.asarray(a, np.int32) for a in (gmv_x, gmv_y, pred_off, frac)], axis=1)
+    j = np.stack([_i32(a) for a in (gmv_x, gmv_y, pred_off, frac)], axis=1)
     return torch.from_numpy(np.ascontiguousarray(j)).to(device)
 
 
