@@ -234,6 +234,34 @@ QP_RANGE_CASES = {
     "q0_flat255": (128, 64, 1, 3, 9255, ["--preset", "medium", "-b", "1", "-q", "0"], 1),
     "q51_flat0": (128, 64, 1, 3, 9000, ["--preset", "medium", "-b", "1", "-q", "51"], 1),
 }
+# Picture sizes modulo the 64-sample CTU (Param::finish takes every positive multiple of 8 from 8x8 up): pictures smaller than one CTU in one or both directions, one CU
+# row / one CU column, and partial last CTU columns and rows of every remainder 8 .. 56 -- each remainder once at the right edge and once at the bottom edge.  The search
+# range (32 / 64 / 128 / 384) is larger than most of these pictures, and so is the padding (144 / 72).  A = closed GOP of I + three B pictures, B = low delay.
+_SIZE_A, _SIZE_B = ["--preset", "medium", "--closed-gop", "-I", "4", "-b", "3"], ["--preset", "fast", "-I", "0", "-b", "0"]
+PICTURE_SIZE_CASES = {
+    # below one CTU
+    "size_8x8_noise": (8, 8, 1, 4, 21, _SIZE_A, 1),
+    "size_24x40_moving": (24, 40, 1, 3, 5021, _SIZE_B, 1),
+    "size_56x56_noise": (56, 56, 1, 3, 21, _SIZE_B, 1),
+    "size_64x8_moving": (64, 8, 1, 4, 5021, _SIZE_A, 1),  # one CU row
+    "size_8x64_noise": (8, 64, 1, 4, 21, _SIZE_A, 1),  # one CU column
+    "size_200x8_moving": (200, 8, 1, 3, 5021, _SIZE_B, 1),  # one CU row, four CTUs, remainder 8
+    # partial CTUs: (remainder of the width, of the height)
+    "size_80x88_moving": (80, 88, 1, 4, 5021, _SIZE_A, 1),  # 16, 24
+    "size_104x112_noise": (104, 112, 1, 3, 21, _SIZE_B, 1),  # 40, 48
+    "size_120x72_noise_3gops": (120, 72, 3, 4, 21, _SIZE_A, 1),  # 56, 8
+    "size_88x80_noise": (88, 80, 1, 3, 21, _SIZE_B, 1),  # 24, 16
+    "size_112x104_moving": (112, 104, 1, 4, 5021, _SIZE_A, 1),  # 48, 40
+    "size_72x120_moving": (72, 120, 1, 3, 5021, _SIZE_B, 1),  # 8, 56
+    "size_176x144_noise_m2": (176, 144, 1, 4, 21, _SIZE_A, 2),  # 48, 16; two row chains
+    # presets slow and placebo (the fused walk only)
+    "size_88x80_slow": (88, 80, 1, 4, 5021, ["--preset", "slow"] + _SIZE_A[2:], 1),
+    "size_24x40_placebo": (24, 40, 1, 4, 5021, ["--preset", "placebo"] + _SIZE_A[2:], 1),
+}
+# further sizes on the CPU harness only (the frame loop, the planner and the walk's host side)
+PICTURE_SIZE_HOST_CASES = dict(
+    [("size_%dx%d_moving_host" % (w, h), (w, h, 1, 4, 5021, _SIZE_A, 1)) for w, h in ((16, 8), (8, 24), (32, 32), (40, 72), (72, 40), (208, 80))] +
+    [("size_%dx%d_noise_m2_host" % (w, h), (w, h, 1, 3, 21, _SIZE_B, 2)) for w, h in ((144, 152), (168, 176), (184, 136))])
 # What the PRODUCT library's configuration check (enc_plan.h Param::finish) takes and what it refuses -- ONE table, read by tests/test_enc_host.py through
 # xeve_hip_enc_footprint (no device: a change of the accepted set fails in the build container) and by tests/test_enc_gpu.py through xeve_hip_enc_create.
 # (kwargs of xeve_amd.encode.config beside w / h, accepted?)
@@ -251,6 +279,8 @@ CONFIG_ACCEPTANCE = [
     (dict(w=128, h=64, preset=2, qp_cb_offset=2), False), (dict(w=128, h=64, preset=3, qp_cr_offset=-1), False),
     (dict(w=128, h=64, ref=5), False), (dict(w=128, h=64, ref=2), True),
     (dict(w=128, h=64, bframes=0, keyint=0, closed_gop=True), False),
+    # pictures below one CTU and with partial CTUs (PICTURE_SIZE_CASES code them): the accepted set must not be narrowed quietly
+    (dict(w=8, h=8), True), (dict(w=200, h=8), True), (dict(w=8, h=64), True), (dict(w=176, h=144, threads=2), True),
 ]
 
 

@@ -143,6 +143,32 @@ def test_the_ends_of_the_qp_range_on_the_gpu(name, walk, hip, yuv_dir):
     assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in g["per_gop"]]
 
 
+SIZE_FUSED = ("size_8x8_noise", "size_24x40_moving", "size_104x112_noise", "size_176x144_noise_m2")  # the fused walk's device build at four of the shapes its host side is held at
+
+
+def _picture_size_params():
+    """fast and medium presets: every shape on the composed walk (no host twin), four on the fused kernel; slow and placebo on the fused kernel (the only walk that codes them)"""
+    out = []
+    for n in _enc.PICTURE_SIZE_CASES:
+        fused_only = _enc.PICTURE_SIZE_CASES[n][5][1] in ("slow", "placebo")
+        out += [pytest.param(n, w, id="%s-%s" % (n, WALK_NAME[w])) for w in ((1,) if fused_only else (0, 1) if n in SIZE_FUSED else (0,))]
+    return out
+
+
+@pytest.mark.parametrize("name,walk", _picture_size_params())
+def test_picture_sizes_modulo_the_ctu_on_the_gpu(name, walk, hip, yuv_dir):
+    """pictures smaller than one CTU in one or both directions (8x8, one CU row of one and of four CTUs, one CU column) and partial last CTU columns and rows of every
+    remainder 8 .. 56 through the device path -- frame loading and padding deeper than the picture, the walks' tile loops and neighbour windows, search windows clipped to a
+    picture smaller than the range and than the block, the loop filter, the writers with one CTU column or row: every GOP = the unmodified reference's bytes
+    (tests/golden/enc_v1.json), no harness between"""
+    w, h, gops, frames, seed, cli, threads = _enc.PICTURE_SIZE_CASES[name]
+    g = _enc.golden()["batches"][name]
+    data, fb = _frames(yuv_dir, name, w, h, gops * frames, seed), w * h * 3 // 2 * frames
+    with hip.walk_select(walk):
+        outs, _ = _run(hip, _cfg(hip, w, h, cli, threads), [data[i * fb:(i + 1) * fb] for i in range(gops)], frames)
+    assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in g["per_gop"]]
+
+
 @pytest.mark.parametrize("name", sorted(_e2e.SLOW_CASES))
 def test_preset_slow_single_runs_on_the_gpu(name, hip, yuv_dir):
     """--preset slow on the device (the fused walk: walk_dbk.h estimates the loop filter's share of every candidate's distortion -- rdo_dbk_switch = 1 --, the search

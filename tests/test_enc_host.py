@@ -113,6 +113,24 @@ def test_the_ends_of_the_qp_range_on_the_host_side(name, yuv_dir):
         assert (len(whole), _enc.md5(whole)) == (g["whole"]["bytes"], g["whole"]["md5"])
 
 
+SIZE_CASES = dict(_enc.PICTURE_SIZE_CASES, **_enc.PICTURE_SIZE_HOST_CASES)
+
+
+@pytest.mark.parametrize("name", sorted(SIZE_CASES))
+def test_picture_sizes_modulo_the_ctu_on_the_host_side(name, yuv_dir):
+    """pictures below one CTU (8x8, one CU row, one CU column) and partial last CTU columns / rows of every remainder 8 .. 56: the frame loop, the row chains and the walk's
+    host side at those sizes -- every GOP = the unmodified reference's run over it (the device: tests/test_enc_gpu.py)"""
+    w, h, gops, frames, seed, cli, threads = SIZE_CASES[name]
+    g = _enc.golden()["batches"][name]
+    data, fb = _frames(yuv_dir, name, w, h, gops * frames, seed), w * h * 3 // 2 * frames
+    outs = _enc.encode_cpu(_enc.config(w, h, cli, threads), [data[i * fb:(i + 1) * fb] for i in range(gops)], frames)
+    assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in g["per_gop"]]
+    assert ("whole" in g) == (gops > 1)
+    if gops > 1:
+        whole = b"".join(outs)
+        assert (len(whole), _enc.md5(whole)) == (g["whole"]["bytes"], g["whole"]["md5"])
+
+
 @pytest.mark.parametrize("name", sorted(_e2e.SLOW_CASES))
 def test_preset_slow_single_runs(name, yuv_dir):
     """--preset slow: the search's quarter-pel stage, ME range 128 and rdo_dbk_switch = 1 -- every candidate's distortion includes what the loop filter will do to the CU's

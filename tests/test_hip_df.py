@@ -38,10 +38,13 @@ def test_hip_deblock_matches_reference_goldens():
 
 
 @pytest.mark.parametrize("w,h,bd,idc,min_cu", [(256, 192, 10, 1, 4), (512, 320, 10, 1, 8), (136, 72, 8, 1, 4), (192, 64, 12, 3, 4), (320, 200, 10, 0, 4),
-                                               (1920, 1080, 10, 1, 8)])
+                                               (1920, 1080, 10, 1, 8),
+                                               # pictures below one CTU, one CU row, a partial last CTU column and row (tests/_enc.py PICTURE_SIZE_CASES)
+                                               (8, 8, 10, 1, 4), (24, 40, 10, 1, 4), (64, 8, 10, 1, 8), (200, 8, 10, 1, 4), (88, 80, 10, 1, 8)])
 def test_hip_deblock_vs_oracle(w, h, bd, idc, min_cu):
     O = oracle_df()
     r = np.random.default_rng(w + 3 * h + bd + idc)
+    acted = [0, 0, 0]
     for rep in range(2 if w < 1000 else 1):
         c = make_case(r, w, h, bd, idc, min_cu)
         e = [p.copy() for p in c["planes"]]
@@ -51,6 +54,8 @@ def test_hip_deblock_vs_oracle(w, h, bd, idc, min_cu):
         got = run_hip(c)
         for k in range(3):
             assert np.array_equal(got[k], e[k]), (rep, k, np.argwhere(got[k] != e[k])[:4])
+            acted[k] += int((e[k] != c["planes"][k]).sum())
+    assert all(acted[:3 if idc else 1]), acted  # (the oracle's filter did change samples of every plane, at 8x8 too: an equal "nothing filtered" would prove nothing)
 
 
 def test_hip_deblock_over_the_whole_qp_range_vs_oracle():
@@ -123,7 +128,15 @@ def test_hip_picbuf_expand():
     # a 4:2:0 picture with the reference's padding depths (144 / 72), against the oracle
     O = oracle_df()
     r = np.random.default_rng(7)
-    w, h, el, ec = 320, 192, 144, 72
+    for w, h, el, ec in ((320, 192, 144, 72), (8, 8, 144, 72), (200, 8, 144, 72)):  # (8x8, 200x8: the padding is far deeper than the picture)
+        _expand_vs_oracle(O, r, dev, w, h, el, ec)
+
+
+def _expand_vs_oracle(O, r, dev, w, h, el, ec):
+    import torch
+
+    from xeve_amd import device as D
+
     sl, sc = w + 2 * el, w // 2 + 2 * ec
     pl = [r.integers(0, 1024, size=(h + 2 * el, sl)).astype(np.int16), r.integers(0, 1024, size=(h // 2 + 2 * ec, sc)).astype(np.int16),
           r.integers(0, 1024, size=(h // 2 + 2 * ec, sc)).astype(np.int16)]
