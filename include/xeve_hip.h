@@ -904,7 +904,8 @@ typedef struct xeve_hip_enc_config {
     int32_t threads;          /* -m: 1 .. 8 */
     int32_t inter_slice_type; /* --inter-slice-type: 0 B, 1 P */
     int32_t ref;              /* --ref (0: the preset's) */
-    int32_t reserved[4];      /* [0] bit 0: always run the second writer pass (tests); bit 1: the application's --info 0 (no SEI with the option list); bits 8-15: --level-idc (0: 40).  [1]: the application's -d, the input's bit depth -- 0 / 8: one byte per sample;
+    int32_t reserved[4];      /* [0] bit 0: always run the second writer pass (tests); bit 1: the application's --info 0 (no SEI with the option list); bit 2: measure every picture (xeve_hip_enc_picture_info's
+                               * sse / psnr); bit 3: keep the reconstructed pictures (xeve_hip_enc_recon; w * h * 3 bytes per picture of the batch); bits 8-15: --level-idc (0: 40).  [1]: the application's -d, the input's bit depth -- 0 / 8: one byte per sample;
                                * 10: 16-bit little-endian samples (frames pushed are twice as long).  Either way the codec works at 10 bits (--codec-bit-depth).  [2], [3]: --qp-cb-offset / --qp-cr-offset, -12 .. 12
                                * (pinned against the reference LIBRARY: the application lists the options and cannot parse them; 0 with presets slow / placebo). */
 } xeve_hip_enc_config;
@@ -943,6 +944,33 @@ int xeve_hip_enc_footprint(const xeve_hip_enc_config *cfg, int ngops, int frames
  * hierarchy's offsets over the pictures `frames` frames make -- is so low that a picture of noise would not fit (below 24 at 3840x2160; 7.5 bytes per sample at QP 0).
  * A picture that still outgrows it ends the run with an error, never with a write past the buffer.  No device call. */
 int xeve_hip_enc_slice_capacity(const xeve_hip_enc_config *cfg, int frames, uint64_t *bytes);
+/* What the reference returns with every picture beside its bytes: the application's table row (POC Tid Ftype QP PSNR-Y PSNR-U PSNR-V Bits; cal_psnr / find_psnr_16bit,
+ * app/xeve_app_util.h:660-751, print_psnr, app/xeve_app.c:339-383) and the reconstructed picture (xeve_config(XEVE_CFG_GET_RECON); the application's -r).  Both are taken on
+ * the device at the picture's end, behind the loop filter, and cost nothing unless the run was created with reserved[0] bit 2 (sums) / bit 3 (pictures); neither changes a
+ * byte of the bitstream. */
+typedef struct xeve_hip_enc_picture {
+    int32_t  frame, poc, slice_type, tid, qp, idr; /* frame: display position in the run; slice_type: 0 B, 1 P, 2 I (XEVE_ST_*) */
+    int32_t  coding_pos, reserved;
+    uint64_t bytes;                                /* the picture's access unit as appended to the run's bitstream (parameter sets and SEI in front of an IDR included): the application's Bits / 8 */
+    uint64_t sse[3];                               /* at the codec's 10 bits, against the input widened as the codec sees it */
+    double   psnr[3];                              /* from sse by the application's formula (find_psnr_16bit); 100 when sse is 0 */
+} xeve_hip_enc_picture;
+/* Valid for every picture whose access unit is in xeve_hip_enc_bitstream: after xeve_hip_enc_encode, after the xeve_hip_enc_advance that returns 0 steps, or after
+ * xeve_hip_enc_flush.  Both may wait for the encoder's main stream.  A picture not yet ended, a frame out of range or a run created without the bit a call needs gets
+ * XEVE_HIP_ERR_ARG and a message -- never data of an earlier picture or run.  _picture_info needs bit 2 for the WHOLE record (a run created without it gets no row at all, not a row without sums);
+ * _recon needs bit 3.
+ * _recon: w * h * 3 bytes -- planar Y, U, V, cropped, 16-bit little-endian samples at the codec's 10 bits: what the application's -r file holds for that frame -- into host
+ * (on_device 0) or device memory of the encoder's GPU (1; memory of another GPU or of the host is refused); complete when the call returns. */
+int xeve_hip_enc_picture_info(xeve_hip_enc *e, int gop, int frame, xeve_hip_enc_picture *out);
+int xeve_hip_enc_recon(xeve_hip_enc *e, int gop, int frame, void *dst, int on_device);
+/* The kernel behind both, as a leaf: the w x h interior of `npics` stacked pictures (planes rec[0..2], strides and picture distances in samples; samples at most 10 bits
+ * wide) is copied into `out` -- per picture Y, then U, then V, no padding, pictures out_pic samples apart (NULL: no copy) -- and / or its squared differences against org
+ * are summed per picture and plane into sse[npics][3] (NULL: no measurement, org may be NULL then; otherwise the sums are SET: zeroed on the stream first, not added to;
+ * exact integers, the same bits on every run).  w and h multiples of 8; luma pointers, `out` and luma rows 16-byte aligned (strides and distances multiples of 8 samples,
+ * out_pic too), chroma pointers and rows 8-byte aligned (multiples of 4 samples).  rec and org are only read; nothing outside out[0 .. npics * out_pic) and sse is
+ * written.  Two launches (luma, chroma) whatever npics is; npics at most 65535.  Everything is device memory. */
+int xeve_hip_recon_measure(const uint16_t *const rec[3], int s_rec_l, int s_rec_c, int64_t rec_pic_l, int64_t rec_pic_c, const uint16_t *const org[3], int s_org_l, int s_org_c,
+                           int64_t org_pic_l, int64_t org_pic_c, int w, int h, int npics, uint16_t *out, int64_t out_pic, uint64_t *sse, void *stream);
 
 /* ------------------------------------------------------------------------------------------- */
 /* Main profile: the adaptive loop filter's sample kernels ("ALF           */

@@ -239,6 +239,26 @@ struct xeve_hip_enc {
     double  t_steps = 0, t_ends = 0;
     std::vector<std::vector<uint8_t>> bitstreams;
     std::unique_ptr<BatchEncoder<xeve_hip_enc>> loop; // the frame loop of the run in progress (xeve_hip_enc_begin .. the advance that returns 0)
+    // What the reference returns with every picture beside its bytes (reserved[0] bit 2: the squared differences against the original; bit 3: the reconstructed picture),
+    // taken at the picture's end from the store and from `org` -- both are overwritten soon afterwards.  kept: [display frame][GOP][w * h * 3 / 2] samples, sums:
+    // [display frame][GOP][3].  A picture is SERVED once its access unit is in the bitstream: the frame loop's collect() precedes exactly that append.
+    DevBuf kept, sums;
+    std::vector<PicPlan>  pics;        // the run's pictures in coding order
+    std::vector<int>      coded_at;    // display frame -> coding position
+    std::vector<size_t>   au_at;       // [coding position][GOP]: the bitstream's size in front of the picture's access unit
+    std::vector<uint64_t> h_sums;      // [display frame][GOP][3], read back per picture when first asked for
+    std::vector<char>     sums_read;   // per coding position
+    int n_served = 0;                  // pictures, in coding order, whose access unit is in the bitstream
+    int device = -1;                   // the GPU the batch lives on (create)
+    bool measures() const { return (P_reserved0 & 4) != 0; }
+    bool keeps_recon() const { return (P_reserved0 & 8) != 0; }
+    size_t pic_samples() const { return (size_t)P.w * P.h * 3 / 2; }
+    bool begin_run()
+    {
+        n_served = 0;
+        au_at.assign((size_t)F * G, 0), h_sums.assign((size_t)F * G * 3, 0), sums_read.assign(F, 0);
+        return !measures() || hip_ok(hipMemsetAsync(sums.p, 0, sums.bytes, st), "hipMemset");
+    }
 
     bool fail(const std::string &m)
     {
@@ -275,6 +295,7 @@ struct xeve_hip_enc {
         pos_of_frame.assign(F, -1);
         for(size_t i = 0; i < plan.size(); i++)
             if(plan[i].frame >= 0 && plan[i].frame < F && pos_of_frame[plan[i].frame] < 0) pos_of_frame[plan[i].frame] = (int)i;
+        pics = plan, coded_at = pos_of_frame; // (before the frames' placement below falls back to the display order)
         bool in_order = (int)plan.size() == F;
         for(int f = 0; f < F; f++) in_order = in_order && pos_of_frame[f] >= 0;
         static const bool share = !(getenv("XEVE_HIP_ENC_SHARE") && atoi(getenv("XEVE_HIP_ENC_SHARE")) == 0); // developer switch: 0 = every store in slot_planes
@@ -300,6 +321,8 @@ struct xeve_hip_enc {
             {&jobs, nst * sizeof(xeve_hip_ctu_job)}, {&out, nst * sizeof(xeve_hip_ctu_data)}, {&next_best, nst * sizeof(xeve_hip_sbac)}, {&cost, nst * 8},
             {&slice, (size_t)G * slice_cap}, {&pos, (size_t)G * 4}};
         if(rewrite_mode) v.insert(v.end(), {{&store2[0], store_bytes()}, {&rw_scu, m * 4}, {&rw_cum, m * 4}, {&rw_ipm, m}});
+        if(keeps_recon()) v.push_back({&kept, (size_t)G * F * pic_samples() * 2});
+        if(measures()) v.push_back({&sums, (size_t)G * F * 3 * sizeof(uint64_t)});
         return v;
     }
     size_t store_bytes() const { return (size_t)G * f_lcu * sizeof(xl::CtuSyntax); }
@@ -328,6 +351,7 @@ struct xeve_hip_enc {
         memset(coef_c, 0, sizeof(coef_c));
         for(int i = 0; i < 8; i++) memcpy(coef_c[4 * i], k_coef_c8[i], sizeof(k_coef_c8[i])); // xeve_tbl_mc_c_coeff (xeve_mc.c:59-93)
         int pr_low = 0, pr_high = 0;
+        if(!hip_ok(hipGetDevice(&device), "hipGetDevice")) return false;
         (void)hipDeviceGetStreamPriorityRange(&pr_low, &pr_high);
         const char *pe = getenv("XEVE_HIP_ENC_PRIO"); // developer switch: 1 = the walk's stream above the second pass's
         if(!(pe && atoi(pe) == 1)) pr_low = pr_high = 0;
@@ -477,6 +501,15 @@ struct xeve_hip_enc {
                                        slot_map_refi(S.cur_slot) + (size_t)g * map_pic * 2, slot_map_mv(S.cur_slot) + (size_t)g * map_pic * 4, &S.dp, st),
                       "xeve_hip_deblock"))
                 return;
+        if(measures() || keeps_recon()) { // all G pictures at once, behind the loop filter and ahead of the padding, the next load into `org` and the store's reuse
+            const uint16_t *r[3], *o[3];
+            for(int c = 0; c < 3; c++) r[c] = reinterpret_cast<const uint16_t *>(slot_plane(S.cur_slot, c)), o[c] = org[c].as<uint16_t>();
+            const size_t at = (size_t)S.frame * G;
+            if(!rc_ok(xeve_hip_recon_measure(r, s_l, s_c, pic_l, pic_c, o, P.w, P.w / 2, org_l, org_c, P.w, P.h, G, keeps_recon() ? kept.as<uint16_t>() + at * pic_samples() : nullptr,
+                                             (int64_t)pic_samples(), measures() ? sums.as<uint64_t>() + at * 3 : nullptr, st),
+                      "xeve_hip_recon_measure"))
+                return;
+        }
         fin = states.as<xeve_hip_sbac>(), fin_stride = T;
         hipStream_t ws_ = st;
         if(rewrite) {
@@ -516,6 +549,10 @@ struct xeve_hip_enc {
     bool have_held = false;
     void collect(std::vector<std::vector<uint8_t>> &slice_data, std::vector<uint32_t> &bins)
     {
+        if(n_served < F && (int)bitstreams.size() == G && au_at.size() == (size_t)F * G) { // (the frame loop appends the picture's access unit right behind this call)
+            for(int g = 0; g < G; g++) au_at[(size_t)n_served * G + g] = bitstreams[g].size();
+            n_served++;
+        }
         if(have_held) slice_data.swap(held), bins.swap(held_bins), have_held = false;
         else fetch(slice_data, bins);
     }
@@ -607,6 +644,7 @@ extern "C" int xeve_hip_enc_begin(xeve_hip_enc *e)
         xh_set_error("xeve_hip_enc_begin: the last run consumed its frames (picture stores reuse the memory of frames already coded): push every frame again before the next run");
         return XEVE_HIP_ERR_ARG;
     }
+    if(!e->begin_run()) { xh_set_error("xeve_hip_enc_begin: %s", e->error.c_str()); return XEVE_HIP_ERR_DEVICE; } // (before the object is marked as run)
     e->ran = true, e->pushed = 0;
     std::fill(e->slot_clean.begin(), e->slot_clean.end(), 0);
     e->loop.reset(new BatchEncoder<xeve_hip_enc>(*e, e->P, e->G, e->F));
@@ -656,6 +694,60 @@ extern "C" int xeve_hip_enc_bitstream(xeve_hip_enc *e, int gop, const uint8_t **
 {
     XH_REQUIRE(e && data && bytes && gop >= 0 && gop < (int)e->bitstreams.size());
     *data = e->bitstreams[gop].data(), *bytes = e->bitstreams[gop].size();
+    return XEVE_HIP_OK;
+}
+static_assert(sizeof(xeve_hip_enc_picture) == 88 && offsetof(xeve_hip_enc_picture, bytes) == 32 && offsetof(xeve_hip_enc_picture, sse) == 40 && offsetof(xeve_hip_enc_picture, psnr) == 64,
+              "xeve_hip_enc_picture: the layout xeve_amd/lib.py binds");
+// the coding position of display frame `frame` when its access unit is in the bitstream, else -1 with the error set
+static int served_position(xeve_hip_enc *e, const char *who, int gop, int frame)
+{
+    if(!e || gop < 0 || gop >= e->G || frame < 0 || frame >= e->F) { xh_set_error("%s: GOP or frame out of range", who); return -1; }
+    if(!e->loop || !e->error.empty()) { xh_set_error("%s: %s", who, e->loop ? e->error.c_str() : "no run has begun"); return -1; }
+    const int k = e->coded_at[frame];
+    if(k < 0 || k >= e->n_served) { xh_set_error("%s: frame %d has not ended yet (its access unit is not in the bitstream: advance to the end, or flush)", who, frame); return -1; }
+    return k;
+}
+extern "C" int xeve_hip_enc_picture_info(xeve_hip_enc *e, int gop, int frame, xeve_hip_enc_picture *out)
+{
+    XH_ENTER();
+    XH_REQUIRE(e && out);
+    if(!e->measures()) { xh_set_error("xeve_hip_enc_picture_info: the run was created without reserved[0] bit 2 (measure)"); return XEVE_HIP_ERR_ARG; }
+    const int k = served_position(e, "xeve_hip_enc_picture_info", gop, frame);
+    if(k < 0) return XEVE_HIP_ERR_ARG;
+    const size_t at = (size_t)frame * e->G * 3;
+    if(!e->sums_read[k]) { // (the G pictures of the position at once; the kernel that set them is on the main stream)
+        XH_HIP(hipMemcpyAsync(e->h_sums.data() + at, e->sums.as<uint64_t>() + at, (size_t)e->G * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->st));
+        XH_HIP(hipStreamSynchronize(e->st));
+        e->sums_read[k] = 1;
+    }
+    const PicPlan &pp = e->pics[k];
+    memset(out, 0, sizeof(*out));
+    out->frame = pp.frame, out->poc = pp.poc, out->slice_type = pp.slice_type, out->tid = pp.tid, out->qp = slice_qp(e->P, pp.depth), out->idr = pp.idr, out->coding_pos = k;
+    out->bytes = (k + 1 < e->n_served ? e->au_at[(size_t)(k + 1) * e->G + gop] : e->bitstreams[gop].size()) - e->au_at[(size_t)k * e->G + gop];
+    for(int c = 0; c < 3; c++) { // find_psnr_16bit (app/xeve_app_util.h:660-681)
+        out->sse[c] = e->h_sums[at + (size_t)gop * 3 + c];
+        const double factor = (double)((1 << (BIT_DEPTH - 8)) * (1 << (BIT_DEPTH - 8))), mse = (double)out->sse[c] / ((double)e->P.w * e->P.h / (c ? 4 : 1));
+        out->psnr[c] = mse == 0.0 ? 100. : fabs(10 * log10((255 * 255 * factor) / mse));
+    }
+    return XEVE_HIP_OK;
+}
+extern "C" int xeve_hip_enc_recon(xeve_hip_enc *e, int gop, int frame, void *dst, int on_device)
+{
+    XH_ENTER();
+    XH_REQUIRE(e && dst);
+    if(!e->keeps_recon()) { xh_set_error("xeve_hip_enc_recon: the run was created without reserved[0] bit 3 (keep the reconstructed pictures)"); return XEVE_HIP_ERR_ARG; }
+    if(served_position(e, "xeve_hip_enc_recon", gop, frame) < 0) return XEVE_HIP_ERR_ARG;
+    if(on_device) { // (the copy runs on the encoder's stream: memory of another GPU is not what a device-to-device copy there may be handed)
+        hipPointerAttribute_t a;
+        if(hipPointerGetAttributes(&a, dst) != hipSuccess || a.type == hipMemoryTypeHost || a.device != e->device) {
+            (void)hipGetLastError();
+            xh_set_error("xeve_hip_enc_recon: dst is not device memory of the encoder's GPU (%d)", e->device);
+            return XEVE_HIP_ERR_ARG;
+        }
+    }
+    XH_HIP(hipMemcpyAsync(dst, e->kept.as<uint16_t>() + ((size_t)frame * e->G + gop) * e->pic_samples(), e->pic_samples() * 2, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                          e->st));
+    XH_HIP(hipStreamSynchronize(e->st));
     return XEVE_HIP_OK;
 }
 extern "C" int xeve_hip_enc_stats(xeve_hip_enc *e, int64_t *ctu_steps, double *step_seconds, double *picture_end_seconds)

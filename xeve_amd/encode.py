@@ -6,17 +6,32 @@ import ctypes as C
 from . import lib as _lib
 
 PRESETS = {"fast": 0, "medium": 1, "slow": 2, "placebo": 3}
+SLICE_TYPES = "BPI"  # XEVE_ST_B / _P / _I
+
+
+def psnr(sse, samples, bit_depth=10):
+    """the application's PSNR of a plane from its sum of squared differences (find_psnr_16bit: 100 when the planes are equal)"""
+    import math
+
+    mse = sse / samples
+    return 100.0 if mse == 0 else abs(10 * math.log10(255 * 255 * (1 << (bit_depth - 8)) ** 2 / mse))
+
+
+def stats_line(p):
+    """one picture as the application's table prints it: POC Tid Ftype QP PSNR-Y PSNR-U PSNR-V Bits"""
+    return "%-7d%-5d(%s)     %-5d%-10.4f%-10.4f%-10.4f%-10d" % (p["poc"], p["tid"], p["type"], p["qp"], p["psnr"][0], p["psnr"][1], p["psnr"][2], p["bytes"] * 8)
 
 
 def config(w, h, qp=32, keyint=0, bframes=15, closed_gop=False, preset="medium", threads=1, fps=(30, 1), ref=0, always_second_pass=False, input_depth=8, level_idc=40, sei_info=True,
-           inter_slice_type=0, qp_cb_offset=0, qp_cr_offset=0):
+           inter_slice_type=0, qp_cb_offset=0, qp_cr_offset=0, measure=False, keep_recon=False):
     """the options of the reference application (xeve_app: -w -h -q -I -b --closed-gop --preset -m -z --ref -d; --inter-slice-type 0 B / 1 P, --qp-cb-offset,
-    --qp-cr-offset as the reference LIBRARY takes them) as the library's configuration record"""
+    --qp-cr-offset as the reference LIBRARY takes them) as the library's configuration record.  measure: per-picture SSE / PSNR (BatchEncoder.pictures);
+    keep_recon: the reconstructed pictures stay on the device (BatchEncoder.recon; w * h * 3 bytes per picture of the batch) -- neither changes the bitstream"""
     c = _lib.EncConfig()
     c.w, c.h, c.fps_num, c.fps_den, c.qp, c.keyint, c.bframes, c.closed_gop = w, h, fps[0], fps[1], qp, keyint, bframes, int(bool(closed_gop))
     c.preset, c.threads, c.inter_slice_type, c.ref = PRESETS[preset] if isinstance(preset, str) else int(preset), threads, int(inter_slice_type), ref
     c.reserved[2], c.reserved[3] = int(qp_cb_offset), int(qp_cr_offset)
-    c.reserved[0] = (1 if always_second_pass else 0) | (0 if sei_info else 2) | ((int(level_idc) & 0xFF) << 8)  # (--info 0, --level-idc)
+    c.reserved[0] = (1 if always_second_pass else 0) | (0 if sei_info else 2) | (4 if measure else 0) | (8 if keep_recon else 0) | ((int(level_idc) & 0xFF) << 8)  # (--info 0, --level-idc)
     c.reserved[1] = int(input_depth)
     return c
 
@@ -101,6 +116,37 @@ class BatchEncoder:
             out.append(C.string_at(p.value, n.value) if n.value else b"")
         return out
 
+    def picture(self, gop, frame):
+        """the application's table row of one picture (config(measure=True)) -- xeve_hip_enc_picture_info; raises for a picture whose access unit is not in the bitstream yet"""
+        p = _lib.EncPicture()
+        _lib.check(self._L.xeve_hip_enc_picture_info(self._h, int(gop), int(frame), C.byref(p)))
+        return {"frame": p.frame, "poc": p.poc, "type": SLICE_TYPES[p.slice_type], "tid": p.tid, "qp": p.qp, "idr": bool(p.idr), "coding_pos": p.coding_pos, "bytes": int(p.bytes),
+                "sse": [int(v) for v in p.sse], "psnr": [float(v) for v in p.psnr]}
+
+    def pictures(self, gop):
+        """every picture of one GOP in display order (a list of dicts: frame, poc, type 'I' / 'P' / 'B', tid, qp, idr, coding_pos, bytes, sse[3], psnr[3])"""
+        return [self.picture(gop, f) for f in range(self.frames)]
+
+    def recon(self, gop, frame=None):
+        """the reconstructed picture (config(keep_recon=True)) as the application's -r writes it: planar Y, U, V, cropped, 16-bit little-endian samples at the codec's 10 bits
+        (w * h * 3 bytes); frame=None: the whole run in display order -- that run's -r file"""
+        n = self.cfg.w * self.cfg.h * 3
+        frames = range(self.frames) if frame is None else [int(frame)]
+        buf = C.create_string_buffer(n * len(frames))
+        for i, f in enumerate(frames):
+            _lib.check(self._L.xeve_hip_enc_recon(self._h, int(gop), f, C.byref(buf, i * n), 0))
+        return buf.raw
+
+    def recon_into(self, gop, frame, tensor):
+        """the same picture, device to device, into a contiguous uint8 / int16 torch tensor of w * h * 3 bytes on the encoder's GPU (complete when the call returns)"""
+        import torch
+
+        assert tensor.is_cuda and tensor.is_contiguous() and tensor.dtype in (torch.uint8, torch.int16)
+        assert tensor.numel() * tensor.element_size() == self.cfg.w * self.cfg.h * 3  # (the library refuses memory of another GPU than the encoder's)
+        torch.cuda.current_stream(tensor.device).synchronize()  # (the library copies on its own stream: nothing queued on torch's may still use the tensor)
+        _lib.check(self._L.xeve_hip_enc_recon(self._h, int(gop), int(frame), C.c_void_p(tensor.data_ptr()), 1))
+        return tensor
+
     def stats(self):
         steps, a, b = C.c_int64(), C.c_double(), C.c_double()
         _lib.check(self._L.xeve_hip_enc_stats(self._h, C.byref(steps), C.byref(a), C.byref(b)))
@@ -168,10 +214,11 @@ def plan_batches(cfg, ngops, frames, free_bytes, max_batches=3, reserve_bytes=8 
     return rounds
 
 
-def encode_gops(cfg, ngops, frames, feed, free_bytes=None, max_batches=3, batch_gops=None):
+def encode_gops(cfg, ngops, frames, feed, free_bytes=None, max_batches=3, batch_gops=None, collect=None):
     """codes `ngops` closed GOPs of `frames` pictures each on the current GPU and returns their bitstreams in order.  feed(encoder, first_gop, count) pushes the frames of
     GOPs [first_gop, first_gop + count) into `encoder` as its GOPs 0 .. count - 1.  The GOPs are cut into batches by plan_batches; the batches of a round are encoded
-    side by side, one host thread each (the library call releases the GIL)."""
+    side by side, one host thread each (the library call releases the GIL).  collect(first_gop, encoder) is called after each batch's encode, before the batch is
+    closed, in the order of the GOPs: the place to read pictures() / recon() of a configuration with measure / keep_recon."""
     import concurrent.futures as cf
 
     if free_bytes is None:
@@ -188,16 +235,34 @@ def encode_gops(cfg, ngops, frames, feed, free_bytes=None, max_batches=3, batch_
                 results = list(ex.map(lambda e: e.encode(), encs))
             for (first, n), streams in zip(batches, results):
                 out[first:first + n] = streams
+            if collect is not None:
+                for e, (first, _) in zip(encs, batches):
+                    collect(first, e)
         finally:
             for e in encs:
                 e.close()
     return out
 
 
-def encode_file(yuv_path, out_path, cfg, gops, frames, max_batches=3):
+def encode_file(yuv_path, out_path, cfg, gops, frames, max_batches=3, recon_path=None, stats_path=None):
     """the whole sequence: GOP g = frames [g * frames, (g + 1) * frames) of the file; the concatenated bitstreams are what the reference writes for the same sequence
-    with --closed-gop -I frames.  Sequences beyond one batch are cut into batches that run side by side (encode_gops)."""
+    with --closed-gop -I frames.  Sequences beyond one batch are cut into batches that run side by side (encode_gops).  recon_path: the reconstructed
+    sequence, GOP after GOP in display order -- the reference's -r file of the same run; stats_path: one line per picture as the application's table prints it (POC Tid
+    Ftype QP PSNR-Y PSNR-U PSNR-V Bits), every GOP in coding order.  Either switches the configuration's measure / keep_recon on for this call."""
+    if recon_path or stats_path:
+        c = _lib.EncConfig.from_buffer_copy(cfg)
+        c.reserved[0] |= (8 if recon_path else 0) | (4 if stats_path else 0)
+        cfg = c
     fb = cfg.w * cfg.h * 3 // 2 * (2 if cfg.reserved[1] > 8 else 1)
+    recon_file, stats_file = open(recon_path, "wb") if recon_path else None, open(stats_path, "w") if stats_path else None
+
+    def collect(first, enc):  # (encode_gops calls it in the order of the GOPs)
+        for g in range(enc.ngops):
+            if recon_file:
+                recon_file.write(enc.recon(g))
+            if stats_file:
+                for p in sorted(enc.pictures(g), key=lambda p: p["coding_pos"]):
+                    stats_file.write(stats_line(p) + "\n")
 
     def feed(enc, first, n):
         with open(yuv_path, "rb") as f:
@@ -206,7 +271,12 @@ def encode_file(yuv_path, out_path, cfg, gops, frames, max_batches=3):
                 for k in range(frames):
                     enc.push(g, k, f.read(fb))
 
-    streams = encode_gops(cfg, gops, frames, feed, max_batches=max_batches)
+    try:
+        streams = encode_gops(cfg, gops, frames, feed, max_batches=max_batches, collect=collect if recon_file or stats_file else None)
+    finally:
+        for f in (recon_file, stats_file):
+            if f:
+                f.close()
     with open(out_path, "wb") as f:
         for s in streams:
             f.write(s)

@@ -49,6 +49,10 @@ class EncConfig(C.Structure):  # xeve_hip_enc_config
     _fields_ = [(n, C.c_int32) for n in "w h fps_num fps_den qp keyint bframes closed_gop preset threads inter_slice_type ref".split()] + [("reserved", C.c_int32 * 4)]
 
 
+class EncPicture(C.Structure):  # xeve_hip_enc_picture (88 B)
+    _fields_ = [(n, C.c_int32) for n in "frame poc slice_type tid qp idr coding_pos reserved".split()] + [("bytes", C.c_uint64), ("sse", C.c_uint64 * 3), ("psnr", C.c_double * 3)]
+
+
 class InterParams(C.Structure):  # xeve_hip_inter_params
     _fields_ = [("rdo", RdoParams), ("me", EpzsParams), ("refi_bits", (C.c_int32 * 8) * 2), ("range_recentre", (C.c_int32 * 8) * 2), ("max_cand", C.c_int32),
                 ("poc", C.c_int32), ("col_list_poc0", C.c_int32), ("pad_", C.c_int32), ("skip_th", C.c_double)]
@@ -270,6 +274,9 @@ FUNCTIONS = {
     "xeve_hip_enc_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "xeve_hip_enc_footprint": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "xeve_hip_enc_slice_capacity": (c_int, [c_void_p, c_int, c_void_p]),
+    "xeve_hip_enc_picture_info": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "xeve_hip_enc_recon": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),
+    "xeve_hip_recon_measure": (c_int, [c_void_p, c_int, c_int, c_i64, c_i64, c_void_p, c_int, c_int, c_i64, c_i64, c_int, c_int, c_int, c_void_p, c_i64, c_void_p, c_void_p]),
 }
 TABLES = {
     "xeve_tbl_sad_16b_hip": FN_SAD * 64,
