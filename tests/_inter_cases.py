@@ -39,6 +39,25 @@ def make_inter_picture(r, w, h, bd, nref, idc=1, slice_type=0, gop=8):
     return refs, org
 
 
+def make_degenerate_picture(r, w, h, bd, nref, idc=1, slice_type=0, kind="flat"):
+    """the tables and POCs of make_inter_picture, but every plane of every reference picture and of the original equals one base: mid-grey (kind "flat") or a random tile
+    repeated (kind "periodic": 16x16 luma, 8x8 chroma).  Identical reference pictures make refi 0 against refi 1, list 0 against list 1 and uni against bi exact ties --
+    the reference keeps the first of equals everywhere -- and periodic ones add ties between the candidates of one search"""
+    refs, org = make_inter_picture(r, w, h, bd, nref, idc, slice_type)
+    for k in range(3):
+        shape = org[k].shape
+        if kind == "flat":
+            base = np.full(shape, 1 << (bd - 1), np.int16)
+        else:
+            t = 16 if k == 0 else 8
+            base = np.tile(r.integers(0, 1 << bd, size=(t, t)).astype(np.int16), (shape[0] // t + 1, shape[1] // t + 1))[:shape[0], :shape[1]]
+        org[k][:] = base
+        for pic in refs["pics"]:
+            pic[k][:] = base
+    refs["shifts"] = [(0, 0)] * len(refs["pics"])
+    return refs, org
+
+
 def refi_bits(num_refp, refi):
     """xeve_tbl_refi_bits[num_refp][refi] (xeve_tbl.c:498-517) in closed form"""
     return 0 if num_refp < 2 else min(refi + 1, num_refp - 1)

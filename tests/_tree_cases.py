@@ -94,7 +94,7 @@ def run_oracle_picture(c, p):
 
 
 # ---- P / B slices: one picture with its reference pictures; the CTUs coded in raster order from clean maps -------------------------------------------------------
-from _inter_cases import make_inter_params, make_inter_picture  # noqa: E402
+from _inter_cases import make_degenerate_picture, make_inter_params, make_inter_picture  # noqa: E402
 from _libs import InterParams  # noqa: E402
 from _mc_cases import refpic_table  # noqa: E402
 
@@ -109,9 +109,15 @@ INTER_CASES = [(4101, 128, 64, 10, 1, 1, 1, 0, 0.0), (4102, 128, 64, 10, 1, 0, 2
                (4105, 128, 128, 10, 1, 0, 2, 0, 6.0)]
 
 
-def make_inter_case(seed, w, h, bd, idc, slice_type, nref, odd_poc, skip_th):
+# the same on degenerate pictures (_inter_cases.make_degenerate_picture: all reference pictures and the original one flat or periodic base, the rectangle patches below
+# on top, so that the tree still splits and intra wins somewhere): the last field is the content.  A list of its own: tests/golden/tree_v1.npz records INTER_CASES
+DEGENERATE_INTER_CASES = [(4901, 128, 64, 10, 1, 0, 2, 0, 0.0, "periodic"), (4902, 64, 64, 10, 1, 1, 1, 1, 0.0, "periodic"), (4903, 128, 64, 10, 1, 0, 2, 1, 6.0, "flat"),
+                          (4904, 72, 88, 8, 1, 0, 1, 0, 0.0, "flat")]
+
+
+def make_inter_case(seed, w, h, bd, idc, slice_type, nref, odd_poc, skip_th, content=None):
     r = np.random.default_rng(seed)
-    refs, org = make_inter_picture(r, w, h, bd, nref, idc, slice_type)
+    refs, org = make_inter_picture(r, w, h, bd, nref, idc, slice_type) if content is None else make_degenerate_picture(r, w, h, bd, nref, idc, slice_type, content)
     # local motion and new content, so that the tree splits and intra CUs win somewhere: rectangles of the original replaced by a differently shifted copy of
     # itself, by noise, or by a flat patch (chroma follows)
     ws_, hs_ = refs["ws"], refs["hs"]
@@ -149,7 +155,7 @@ def make_inter_case(seed, w, h, bd, idc, slice_type, nref, odd_poc, skip_th):
     col = [r.integers(-24, 25, size=(nscu, 2, 2)).astype(np.int16) for _ in range(2)]
     entry = make_states(r, 1)
     order = [(x, y) for y in range(0, h, 64) for x in range(0, w, 64)]
-    return dict(refs=refs, org=org, mod=mod, maps=maps, col=col, P=P, ipar=ipar, entry=entry, idc=idc, w=w, h=h, order=order, ecu_depth=2 if odd_poc else 4, slice_type=slice_type)
+    return dict(refs=refs, org=org, mod=mod, maps=maps, col=col, P=P, ipar=ipar, entry=entry, idc=idc, w=w, h=h, order=order, ecu_depth=2 if odd_poc else 4, slice_type=slice_type, content=content)
 
 
 def oracle_tree_any():

@@ -104,6 +104,85 @@ def test_hip_pinter_analyze_cu_vs_oracle(w, h, bd, nref, idc, slice_type, skip_t
     assert len(modes) >= (4 if slice_type == 0 else 2), modes
 
 
+def identical_reference_case(kind):
+    """64x64, B slice, two reference pictures per list, every plane of every picture one flat or periodic base (_inter_cases.make_degenerate_picture); per CU size 8 to 64
+    40 jobs with the generator's predictors, every other job's made integer-pel and the same in both lists -> refs, org, states, [(params, jobs)]"""
+    from _inter_cases import make_degenerate_picture
+
+    r = np.random.default_rng(8800 + (kind == "periodic"))
+    w = h = 64
+    refs, org = make_degenerate_picture(r, w, h, 10, 2, 1, 0, kind)
+    st = states(r, 5)
+    sets = []
+    for lw in (3, 4, 5, 6):
+        P = make_inter_params(r, lw, w, h, 10, 2, 1, 0, refs)
+        jobs = make_inter_jobs(r, 40, w, h, 1 << lw, len(st), refs, 0)
+        jobs["mvp"][::2, 0] &= ~3
+        jobs["mvp"][::2, 1] = jobs["mvp"][::2, 0]
+        sets.append((P, jobs))
+    return refs, org, st, sets
+
+
+def oracle_identical_reference_case(refs, org, st, sets):
+    O = oracle_inter()
+    tab = refpic_table(refs, lambda a, off: int(a.ctypes.data) + 2 * off)
+    org_ptrs = np.array([int(org[0].ctypes.data) + 2 * refs["org_l"], int(org[1].ctypes.data) + 2 * refs["org_c"], int(org[2].ctypes.data) + 2 * refs["org_c"]], np.uint64)
+    out = []
+    for P, jobs in sets:
+        cu = 1 << P.rdo.log2_cuw
+        nc = (cu >> refs["ws"]) * (cu >> refs["hs"])
+        for i in range(len(jobs)):
+            er, eb = np.zeros(1, INTER_RESULT_DTYPE), np.zeros(1, SBAC_DTYPE)
+            ec = [np.zeros(cu * cu, np.int16), np.zeros(nc, np.int16), np.zeros(nc, np.int16)]
+            ep = [x.copy() for x in ec]
+            O.xo_pinter_analyze_cu(ptr(org_ptrs), refs["s_l"], refs["s_c"], ptr(tab), refs["s_l"], refs["s_c"], ptr(st), P, ptr(jobs[i:i + 1]), ptr(er), ptr(ec[0]), ptr(ec[1]),
+                                   ptr(ec[2]), ptr(ep[0]), ptr(ep[1]), ptr(ep[2]), ptr(eb))
+            out.append((er, ec, ep, eb))
+    return out
+
+
+def per_list_search(refs, org, P, job, lst):
+    """(cost, mv) of the oracle's pinter_me_epzs for reference picture 0 of one list, from the job's first predictor of that list, with the analysis' own parameters"""
+    import ctypes as C
+
+    from _libs import EpzsParams, MeParams, SpelParams, oracle_epzs
+
+    O = oracle_epzs()
+    me = MeParams.from_buffer_copy(bytes(P.me))
+    me.refi_bits, me.range_recentre, me.bi = P.refi_bits[lst][0], P.range_recentre[lst][0], 0
+    ep = EpzsParams(me, SpelParams(0, 0, 0, 0, P.spel.hpel_cnt, P.spel.qpel_cnt))
+    mvp, mv = np.array(job["mvp"][lst][0], np.int16), np.zeros(2, np.int16)
+    cost = O.xo_me_epzs(ptr(org[0], refs["org_l"]), refs["s_l"], None, ptr(refs["pics"][lst][0], refs["org_l"]), refs["s_l"], int(job["x"]), int(job["y"]), ptr(mvp), ptr(mv),
+                        P.rdo.log2_cuw, P.rdo.log2_cuw, P.rdo.bit_depth, O.mc_l_coeff, C.byref(ep))
+    return cost, int(mv[0]), int(mv[1])
+
+
+@pytest.mark.parametrize("kind", ["flat", "periodic"])
+def test_hip_pinter_analyze_cu_on_identical_reference_pictures(kind):
+    """all reference pictures and the original identical: the two reference indices of a list, list 0 against list 1 and uni against bi end at exactly equal costs, and on
+    periodic content so do candidates inside one search -- the first in the reference's order wins every time.  At least a third of the jobs must have list-0 and list-1
+    searches that end at the same cost and vector.  (The result record holds RD costs per mode, which differ between the lists by the bits of the direction; so the count is
+    taken from the oracle's search itself, pinter_me_epzs per list, on the CPU first.)"""
+    refs, org, st, sets = identical_reference_case(kind)
+    tied = sum(per_list_search(refs, org, P, j, 0) == per_list_search(refs, org, P, j, 1) for P, jobs in sets for j in jobs)
+    print(kind, "jobs whose list-0 and list-1 searches end at the same cost and vector:", tied, "of", sum(len(j) for _, j in sets))
+    assert 3 * tied >= sum(len(j) for _, j in sets)
+    exp = oracle_identical_reference_case(refs, org, st, sets)
+    assert not any((e[0]["refi"][0] == 1).any() for e in exp)  # (reference picture 1 equals reference picture 0 and costs a bit more)
+    k = 0
+    for P, jobs in sets:
+        res, coef, rec, best = run_hip(refs, org, st, P, jobs)
+        got = mask_unobservable(res, 0)
+        for i in range(len(jobs)):
+            er, ec, ep, eb = exp[k]
+            key = (kind, P.rdo.log2_cuw, i, jobs[i], res[i], er[0])
+            assert got[i:i + 1].tobytes() == mask_unobservable(er, 0).tobytes(), key
+            for j in range(3):
+                assert np.array_equal(coef[j][i], ec[j]) and np.array_equal(rec[j][i], ep[j]), (j,) + key
+            assert best[i:i + 1].tobytes() == eb.tobytes(), key
+            k += 1
+
+
 def test_hip_pinter_analyze_cu_edge_cases():
     """empty batch; parameters outside the path are refused with an error code and a message (no silent fallback); one CU at the picture corner"""
     import torch

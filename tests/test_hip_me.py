@@ -1,17 +1,33 @@
 """GPU suite: xeve_hip_me_ipel_diamond_jobs (one complete me_ipel_diamond per wave) against the reference goldens and
-against the oracle on batches of seeded jobs."""
+against the oracle on batches of seeded jobs; the same for the sub-pel pattern and the whole pinter_me_epzs.  Beside noise and texture: content where candidates tie
+and search windows clip (_me_cases: flat, periodic, outward, static) -- the first candidate in evaluation order must win among equal costs, which the lane-parallel
+search gets from a wave minimum, a ballot and the first set bit, and from `<` across the passes of a candidate list longer than a wave."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from _me_cases import PAD, make_job, make_planes, run_oracle
+from _me_cases import PAD, make_planes, run_oracle
 from _me_golden import golden_cases
 
 pytestmark = pytest.mark.gpu
 
 
-def gpu_run(cases):
+_planes_on_device = []  # [(numpy plane, tensor)]: the last few planes sent, so that the rows of a fixture that share a plane pair do not send it once per launch
+
+
+def plane_on_device(a, dev):
+    import torch
+
+    for k, t in _planes_on_device:
+        if k is a:
+            return t
+    _planes_on_device.append((a, torch.from_numpy(a).to(dev)))
+    del _planes_on_device[:-4]
+    return _planes_on_device[-1][1]
+
+
+def gpu_run(cases, bit_depth=10):
     """all cases share planes, block size and every launch-level parameter"""
     import torch
 
@@ -30,9 +46,9 @@ def gpu_run(cases):
         bi_buf[i] = c["org_bi"]
     P = lib.MeParams(c0["lambda_mv"], 1, c0["mot_other"], c0["bi"], c0["faststep"], c0["msr"], c0["sr"], (C.c_int32 * 2)(*c0["min_clip"]),
                      (C.c_int32 * 2)(*c0["max_clip"]), 0)
-    org, ref = torch.from_numpy(c0["org"]).to(dev), torch.from_numpy(c0["ref"]).to(dev)
+    org, ref = plane_on_device(c0["org"], dev), plane_on_device(c0["ref"], dev)
     o0 = PAD * c0["s"] + PAD
-    return D.me_ipel_diamond_jobs(org, o0, c0["s"], torch.from_numpy(bi_buf).to(dev), ref, o0, c0["s"], jobs, S.bit_length() - 1, 10, P)
+    return D.me_ipel_diamond_jobs(org, o0, c0["s"], torch.from_numpy(bi_buf).to(dev), ref, o0, c0["s"], jobs, S.bit_length() - 1, bit_depth, P)
 
 
 def test_me_matches_reference_goldens():
@@ -48,33 +64,22 @@ def test_me_matches_reference_goldens():
 @pytest.mark.parametrize("bi", [0, 1, 2])
 @pytest.mark.parametrize("textured", [False, True])
 def test_me_batches_vs_oracle(S, bi, textured):
-    r = np.random.default_rng(1000 + S + bi * 7 + textured)
-    pl = make_planes(r, textured)
-    base = make_job(r, pl, S, bi)
-    cases = []
-    for _ in range(150):
-        c = make_job(r, pl, S, bi)
-        for k in ("lambda_mv", "mot_other", "faststep", "msr", "sr"):  # launch-level parameters are shared
-            c[k] = base[k]
-        # the job's own range must be derived with the shared search range
-        sr = base["sr"]
-        cx = min(max(c["x"] + ((c["gmvp"][0] - (c["x"] << 2)) >> 2), c["min_clip"][0]), c["max_clip"][0])
-        cy = min(max(c["y"] + ((c["gmvp"][1] - (c["y"] << 2)) >> 2), c["min_clip"][1]), c["max_clip"][1])
-        c["range"] = [min(max(cx - sr, c["min_clip"][0]), c["max_clip"][0]), min(max(cy - sr, c["min_clip"][1]), c["max_clip"][1]),
-                      min(max(cx + sr, c["min_clip"][0]), c["max_clip"][0]), min(max(cy + sr, c["min_clip"][1]), c["max_clip"][1])]
-        cases.append(c)
-    got = gpu_run(cases)
+    from _me_cases import BATCH_STEPS, batch_launches
+
     steps = set()
-    for i, c in enumerate(cases):
-        e = run_oracle(c)
-        g = got[i]
-        assert (int(g["cost"]), int(g["mv"][0]), int(g["mv"][1]), int(g["beststep"]), int(g["best_mv_bits"])) == \
-               (e.cost, e.mv[0], e.mv[1], e.beststep, e.best_mv_bits), (S, bi, textured, i)
-        steps.add(e.beststep)
-    assert len(steps) >= 1
+    for cases in batch_launches(S, bi, textured):
+        got = gpu_run(cases)
+        for i, c in enumerate(cases):
+            e = run_oracle(c)
+            g = got[i]
+            assert (int(g["cost"]), int(g["mv"][0]), int(g["mv"][1]), int(g["beststep"]), int(g["best_mv_bits"])) == \
+                   (e.cost, e.mv[0], e.mv[1], e.beststep, e.best_mv_bits), (S, bi, textured, i)
+            steps.add(e.beststep)
+    # the searches end in the dense round and at several ring sizes: as many distinct values as the oracle gives on the CPU (tests/test_me_degenerate.py)
+    assert len(steps) >= BATCH_STEPS[(S, bi, textured)] and (bi == 1 or len(steps) >= 3), sorted(steps)
 
 
-def gpu_run_spel(cases):
+def gpu_run_spel(cases, bit_depth=10):
     import torch
 
     import xeve_amd
@@ -91,9 +96,9 @@ def gpu_run_spel(cases):
         jobs[i] = (c["x"], c["y"], i * S * S, c["gmvp"], c["mvi"])
         bi_buf[i] = c["org_bi"]
     P = lib.SpelParams(c0["lambda_mv"], 1, c0["mot_other"], c0["bi"], c0["hpel_cnt"], c0["qpel_cnt"])
-    org, ref = torch.from_numpy(c0["org"]).to(dev), torch.from_numpy(c0["ref"]).to(dev)
+    org, ref = plane_on_device(c0["org"], dev), plane_on_device(c0["ref"], dev)
     o0 = PAD * c0["s"] + PAD
-    return D.me_spel_pattern_jobs(org, o0, c0["s"], torch.from_numpy(bi_buf).to(dev), ref, o0, c0["s"], jobs, S.bit_length() - 1, 10, P)
+    return D.me_spel_pattern_jobs(org, o0, c0["s"], torch.from_numpy(bi_buf).to(dev), ref, o0, c0["s"], jobs, S.bit_length() - 1, bit_depth, P)
 
 
 def test_spel_matches_reference_goldens():
@@ -206,3 +211,110 @@ def test_hip_epzs_raster_search_and_integer_refinement_vs_oracle(S):
             if raster and bi == 0:
                 rastered += run_oracle_epzs(dict(c, raster=0), with_mot=True) != e
     assert rastered > 0
+
+
+# ---- where candidates tie and search windows clip ------------------------------------------------------------------------------------------------------------------
+def gpu_run_epzs(cases, bit_depth=10):
+    """xeve_hip_me_epzs_jobs for cases that share planes, block size, bi and every launch-level parameter (raster, refi and the sub-pel counts among them) -> cost, mv, mot_bits"""
+    import torch
+
+    import xeve_amd
+    from xeve_amd import me
+
+    xeve_amd.init(0)
+    dev = torch.device("cuda:0")
+    c0 = cases[0]
+    org, ref = plane_on_device(c0["org"], dev), plane_on_device(c0["ref"], dev)
+    o0 = PAD * c0["s"] + PAD
+    org_bi = torch.from_numpy(np.stack([c["org_bi"] for c in cases])).to(dev)
+    return me.epzs_search_device(org, o0, c0["s"], ref, o0, c0["s"], [c["x"] for c in cases], [c["y"] for c in cases], [c["mvp"] for c in cases], c0["S"].bit_length() - 1,
+                                 bit_depth, c0["lambda_mv"], 1, c0["msr"], c0["sr"], c0["min_clip"], c0["max_clip"], c0["hpel_cnt"], c0["qpel_cnt"], bi=c0["bi"], org_bi=org_bi,
+                                 mv_start=[c["mv0"] for c in cases], extra_bits=c0["mot_other"], with_mot_bits=True, raster=bool(c0["raster"]), refi=c0["refi"])
+
+
+def test_me_degenerate_matches_reference_goldens():
+    """every row of tests/golden/me_degenerate_v1.npz -- the reference's own results on flat, periodic, outward and static content, bit depth 8 / 10 / 12 -- through the three
+    entry points: the diamond, the 8 + 8 point sub-pel pattern, pinter_me_epzs plain, with the raster search (refi 0 / 1) and with the integer refinement"""
+    from _me_cases import EPZS_VARIANTS, GOLDEN_SETS, epzs_variant_of, spel_case_of
+    from _me_golden import golden_degenerate_cases
+
+    n = 0
+    for key, bd, c, dia, sp, ep in golden_degenerate_cases():
+        g = gpu_run([c], bd)[0]
+        assert (int(g["cost"]), int(g["mv"][0]), int(g["mv"][1]), int(g["beststep"])) == dia, (key, n, c["S"], c["bi"])
+        g = gpu_run_spel([spel_case_of(c)], bd)[0]
+        assert (int(g["cost"]), int(g["mv"][0]), int(g["mv"][1])) == sp, (key, n, "spel", c["S"], c["bi"])
+        for v, e in zip(EPZS_VARIANTS, ep):
+            cost, mv, mot = gpu_run_epzs([epzs_variant_of(c, v)], bd)
+            assert (int(cost[0]), int(mv[0, 0]), int(mv[0, 1]), int(mot[0])) == (e[0], e[1], e[2], e[3] if e[3] > 0 else 0), (key, n, "epzs", v, c["S"], c["bi"])
+        n += 1
+    assert n == 24 * len(GOLDEN_SETS)
+
+
+def _diamond_launch_vs_oracle(family, S, bi, bd=10):
+    from _me_cases import assert_family_condition, degenerate_launch
+
+    assert_family_condition(family, S, bi, bd)  # on the CPU, before anything goes to the GPU
+    _, cases, exp = degenerate_launch(family, S, bi, bd)
+    got = gpu_run(cases, bd)
+    for i, (g, e) in enumerate(zip(got, exp)):
+        assert (int(g["cost"]), int(g["mv"][0]), int(g["mv"][1]), int(g["beststep"]), int(g["best_mv_bits"])) == (e.cost, e.mv[0], e.mv[1], e.beststep, e.best_mv_bits), \
+               (family, S, bi, bd, i, cases[i]["x"], cases[i]["y"], cases[i]["gmvp"], cases[i]["range"])
+
+
+TIE_LAUNCHES = [(f, S, bi) for f in ("flat", "periodic4", "periodic8", "periodic16", "periodic32", "outward") for S in (8, 16, 32, 64) for bi in (0, 1, 2)
+                if bi != 1 or f in ("flat", "periodic4", "outward")]  # (bi == 1 has no rings: its 121-candidate round is the two-pass path)
+
+
+@pytest.mark.parametrize("family,S,bi", TIE_LAUNCHES, ids=["%s-%d-%d" % t for t in TIE_LAUNCHES])
+def test_me_ties_and_clipped_windows_vs_oracle(family, S, bi):
+    """100 jobs per launch: flat and periodic4 tie inside the dense round, periodic8 / 16 / 32 in the ring of radius 4 / 8 / 16 (two exact matches at equal vector bits, the
+    earlier one wins), outward has its centre on a clip limit and a cut dense grid.  The oracle is pinned to the reference on this content by tests/test_me_oracle_vs_ref.py."""
+    _diamond_launch_vs_oracle(family, S, bi)
+
+
+@pytest.mark.parametrize("family", ["periodic8", "outward"])
+@pytest.mark.parametrize("bd", [8, 12])
+def test_me_ties_and_clipped_windows_at_bit_depth_8_and_12(family, bd):
+    """the SAD is shifted by bit_depth - 8: at 12 bits four low bits are gone and ordinary content ties; S 8 and 64, bi 0 and 2"""
+    for S in (8, 64):
+        for bi in (0, 2):
+            _diamond_launch_vs_oracle(family, S, bi, bd)
+
+
+SUB_FAMILIES = [("flat", "flat"), ("periodic4", "flat"), ("periodic8", "flat"), ("periodic16", "flat"), ("periodic32", "flat"), ("outward", "flat"), ("static", "flat"),
+                ("static", "periodic")]
+N_SUB = 40
+
+
+@pytest.mark.parametrize("family,kind", SUB_FAMILIES, ids=[f if f != "static" else f + "_" + k for f, k in SUB_FAMILIES])
+def test_spel_ties_vs_oracle(family, kind):
+    """all 8 half-pel and 8 quarter-pel points around an integer-pel predictor equal to the centre: (-2, 0) and (2, 0) cost the same bits, and so do the four quarter-pel
+    axis points -- on flat and flat static content they tie outright, and every job must end on (-2, 0), the first of them"""
+    from _me_cases import degenerate_launch, run_oracle_spel, spel_case_of
+
+    for S in (8, 16, 32, 64):
+        for bi in (0, 1):
+            cases = [spel_case_of(c) for c in degenerate_launch(family, S, bi, 10, kind)[1][:N_SUB]]
+            exp = [run_oracle_spel(c) for c in cases]
+            if family in ("flat", "static") and kind == "flat":  # every SAD is the same: (-2, 0), the first of the four cheapest half-pel points, and no quarter-pel point is cheaper
+                assert all((e.mv[0] - c["mvi"][0], e.mv[1] - c["mvi"][1]) == (-2, 0) for c, e in zip(cases, exp))
+            got = gpu_run_spel(cases)
+            for i, (g, e) in enumerate(zip(got, exp)):
+                assert (int(g["cost"]), int(g["mv"][0]), int(g["mv"][1]), int(g["best_mv_bits"])) == (e.cost, e.mv[0], e.mv[1], e.best_mv_bits), (family, kind, S, bi, i)
+
+
+@pytest.mark.parametrize("family,kind", SUB_FAMILIES, ids=[f if f != "static" else f + "_" + k for f, k in SUB_FAMILIES])
+def test_epzs_ties_and_clipped_windows_vs_oracle(family, kind):
+    """the whole pinter_me_epzs through epzs_search_device on the same content: the first search, the raster search (the periodic16 / 32 launches reach it: their first search
+    ends at step 8 / 16, and from S = 32 on its grid sees one SAD at every point, 81 points for refi 0), the refinement loop (on static and periodic content it re-centres on
+    a zero-SAD plateau), the sub-pel pattern or the integer refinement; cost, vector and mot_bits"""
+    from _me_cases import EPZS_VARIANTS, degenerate_launch, epzs_variant_of, run_oracle_epzs
+
+    for S in (8, 16, 32, 64):
+        for bi, v in [(0, EPZS_VARIANTS[0]), (0, EPZS_VARIANTS[1]), (0, EPZS_VARIANTS[4]), (1, EPZS_VARIANTS[0]), (1, EPZS_VARIANTS[3])]:
+            cases = [epzs_variant_of(c, v) for c in degenerate_launch(family, S, bi, 10, kind)[1][:N_SUB]]
+            cost, mv, mot = gpu_run_epzs(cases)
+            for i, c in enumerate(cases):
+                e = run_oracle_epzs(c, with_mot=True)
+                assert (int(cost[i]), int(mv[i, 0]), int(mv[i, 1]), int(mot[i])) == (e[0], e[1], e[2], e[3] if e[3] > 0 else 0), (family, kind, S, bi, v, i, c["mvp"])

@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 
 from _libs import SBAC_DTYPE
-from _tree_cases import CASES, CTU_DATA_DTYPE, CTU_JOB_DTYPE, INTER_CASES, QP_EDGE_CASES, make_case, make_inter_case, run_oracle_inter_picture, run_oracle_picture
+from _tree_cases import (CASES, CTU_DATA_DTYPE, CTU_JOB_DTYPE, DEGENERATE_INTER_CASES, INTER_CASES, QP_EDGE_CASES, make_case, make_inter_case, run_oracle_inter_picture,
+                         run_oracle_picture)
 
 pytestmark = pytest.mark.gpu
 
@@ -125,27 +126,52 @@ def run_hip_inter_case(c):
     return per_ctu, final
 
 
-@pytest.mark.parametrize("case", INTER_CASES, ids=[str(c[0]) for c in INTER_CASES])
+_oracle_inter_pictures = {}
+
+
+def oracle_inter_picture(case):
+    """the oracle's walk of a case, once for all walk settings: (the case as the oracle left it -- reconstruction and maps updated --, per CTU (data, next state, cost))"""
+    if case not in _oracle_inter_pictures:
+        c = make_inter_case(*case)
+        _oracle_inter_pictures[case] = (c, run_oracle_inter_picture(c))
+    return _oracle_inter_pictures[case]
+
+
+INTRA, INTER, SKIP, DIRECT = 0, 1, 2, 3  # pred_mode of a unit (MODE_INTRA, MODE_INTER, MODE_SKIP, MODE_DIR)
+
+
+@pytest.mark.parametrize("case", INTER_CASES + DEGENERATE_INTER_CASES, ids=[str(c[0]) for c in INTER_CASES + DEGENERATE_INTER_CASES])
 def test_hip_ctu_mode_decision_of_p_and_b_slices_matches_oracle(case):
     """mode_coding_unit on the device: the whole inter analysis, the intra analysis cut against the inter winner where that has a residual, the cheaper one kept;
-    the motion maps updated CU by CU (they are the next CU's merge / MVP candidates); a skipped CU ends the split from a POC-dependent depth on"""
+    the motion maps updated CU by CU (they are the next CU's merge / MVP candidates); a skipped CU ends the split from a POC-dependent depth on.
+    49xx: flat and periodic pictures whose reference pictures are all identical (refi 0 against 1, list 0 against list 1, uni against bi tie exactly; periodic content
+    also ties candidates inside one search) -- the first in the reference's order must win everywhere, and reference index 1 is never chosen"""
     c = make_inter_case(*case)
     got, final = run_hip_inter_case(c)
-    exp = run_oracle_inter_picture(c)  # updates c["mod"], c["maps"] in place
+    c, exp = oracle_inter_picture(case)
     modes = set()
-    for k in range(len(c["order"])):
+    for k, (x, y) in enumerate(c["order"]):
         d, nb, cost = got[k]
         ed, enb, ecost = exp[k]
         for f in CTU_DATA_DTYPE.names:
             assert np.array_equal(d[f][0], ed[f][0]), (case, "ctu", k, f, np.argwhere(d[f][0] != ed[f][0])[:4].tolist())
         assert nb[0:1].tobytes() == enb.tobytes(), (case, k, "coder state")
         assert np.float64(cost[0]).tobytes() == np.float64(ecost).tobytes(), (case, k, cost[0], ecost)
-        modes |= set(np.unique(ed["pred_mode"][0]).tolist())
+        inside = np.zeros((16, 16), bool)  # the CTU's 4x4 units that lie inside the picture
+        inside[:min(64, c["h"] - y) // 4, :min(64, c["w"] - x) // 4] = True
+        modes |= set(np.unique(ed["pred_mode"][0][inside.reshape(-1)]).tolist())
+        if c["content"] is not None and case[6] == 2:
+            assert not (ed["refi"][0] == 1).any(), (case, k, "a unit refers to reference picture 1, which equals reference picture 0 and costs one bit more")
     for j in range(3 if c["idc"] else 1):
         assert np.array_equal(final["mod"][j], c["mod"][j]), (case, "picture", j)
     for f in ("scu", "ipm", "cu_mode", "mv", "refi"):
         assert np.array_equal(final[f].reshape(c["maps"][f].shape), c["maps"][f]), (case, "map", f)
-    assert len(modes) >= 3, modes  # intra, inter and skip CUs all occur
+    if c["content"] is None:
+        assert len(modes) >= 3, modes  # intra, inter and skip CUs all occur
+    elif c["content"] == "periodic":
+        assert modes >= {INTRA, INTER, SKIP}, modes
+    else:  # flat: nothing to search for -- no plain inter CU, but skip and direct ones
+        assert modes >= {INTRA, SKIP, DIRECT}, modes
 
 
 def test_hip_ctu_rows_of_a_b_picture_as_chains_of_one_call():

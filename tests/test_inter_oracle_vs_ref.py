@@ -4,7 +4,7 @@ the reference's own candidate derivation (xeve_get_motion, xeve_get_mv_dir), mot
 import numpy as np
 import pytest
 
-from _inter_cases import make_inter_jobs, make_inter_params, make_inter_picture, mask_unobservable
+from _inter_cases import make_degenerate_picture, make_inter_jobs, make_inter_params, make_inter_picture, mask_unobservable
 from _libs import INTER_RESULT_DTYPE, SBAC_DTYPE, oracle_inter, ptr, ref_inter
 from _mc_cases import refpic_table
 from _rdo_cases import states
@@ -12,10 +12,12 @@ from _rdo_cases import states
 pytestmark = pytest.mark.skipif(ref_inter() is None, reason="oracle/_ref not built (no /root/reference here)")
 
 
-def run_both(w, h, bd, nref, idc, slice_type, skip_th, sizes, n, seed, nref1=None):
+def run_both(w, h, bd, nref, idc, slice_type, skip_th, sizes, n, seed, nref1=None, content=None):
+    """content "flat" / "periodic": every plane of every reference picture and of the original one base (make_degenerate_picture), every other job's predictors integer-pel
+    and the same in both lists"""
     O, R = oracle_inter(), ref_inter()
     r = np.random.default_rng(seed)
-    refs, org = make_inter_picture(r, w, h, bd, nref, idc, slice_type)
+    refs, org = make_inter_picture(r, w, h, bd, nref, idc, slice_type) if content is None else make_degenerate_picture(r, w, h, bd, nref, idc, slice_type, content)
     tab = refpic_table(refs, lambda a, off: int(a.ctypes.data) + 2 * off)
     st = states(r, 5)
     org_ptrs = np.array([int(org[0].ctypes.data) + 2 * refs["org_l"], int(org[1].ctypes.data) + 2 * refs["org_c"], int(org[2].ctypes.data) + 2 * refs["org_c"]],
@@ -25,6 +27,9 @@ def run_both(w, h, bd, nref, idc, slice_type, skip_th, sizes, n, seed, nref1=Non
         cu = 1 << lw
         P = make_inter_params(r, lw, w, h, bd, nref, idc, slice_type, refs, skip_th, nref1=nref1)
         jobs = make_inter_jobs(r, n, w, h, cu, len(st), refs, slice_type)
+        if content is not None:
+            jobs["mvp"][::2, 0] &= ~3
+            jobs["mvp"][::2, 1] = jobs["mvp"][::2, 0]
         nc = max(1, (cu >> refs["ws"]) * (cu >> refs["hs"]))
         for i in range(len(jobs)):
             ra, rb = np.zeros(1, INTER_RESULT_DTYPE), np.zeros(1, INTER_RESULT_DTYPE)
@@ -55,6 +60,14 @@ def run_both(w, h, bd, nref, idc, slice_type, skip_th, sizes, n, seed, nref1=Non
 def test_pinter_analyze_cu(w, h, bd, nref, idc, slice_type):
     modes = run_both(w, h, bd, nref, idc, slice_type, 0.0, [3, 4, 5, 6], 25, 11 * w + h + bd + nref + idc + slice_type)
     assert len(set(modes)) >= (3 if slice_type == 0 else 2), modes
+
+
+@pytest.mark.parametrize("kind", ["flat", "periodic"])
+def test_pinter_analyze_cu_on_identical_reference_pictures(kind):
+    """two reference pictures per list, all identical to each other and to the original: reference index 0 against 1, list 0 against list 1 and uni against bi end at exactly
+    equal costs (on periodic content candidates inside one search too); the oracle must keep the same one of equals as the reference, at every CU size"""
+    modes = run_both(64, 64, 10, 2, 1, 0, 0.0, [3, 4, 5, 6], 40, 8800 + (kind == "periodic"), content=kind)
+    assert len(set(modes)) >= (2 if kind == "periodic" else 1), modes
 
 
 def test_pinter_analyze_cu_skip_threshold():

@@ -21,7 +21,7 @@ def test_mv_bits_table_closed_form():
         assert O.xo_mv_bits(3, mvd) + R.refdrv_refi_bits(1, 0) == R.refdrv_mv_bits(3, mvd, 1, 0), mvd
 
 
-def run_ref(c):
+def run_ref(c, bit_depth=10):
     R = ref_me()
     lg = c["S"].bit_length() - 1
     out = (C.c_int * 4)()
@@ -31,7 +31,7 @@ def run_ref(c):
     mn, mx = np.array(c["min_clip"], np.int32), np.array(c["max_clip"], np.int32)
     # gop_size / poc chosen so that get_range_ipel derives exactly c["sr"]: (msr * |poc - ref_poc| + gop/2) / gop = sr
     gop, poc, ref_poc = c["msr"], c["sr"], 0
-    cost = R.refdrv_me_ipel_diamond(org0, c["s"], ptr(c["org_bi"]), ref0, c["s"], c["x"], c["y"], lg, lg, 10, ptr(rng), ptr(gmvp), ptr(mvi),
+    cost = R.refdrv_me_ipel_diamond(org0, c["s"], ptr(c["org_bi"]), ref0, c["s"], c["x"], c["y"], lg, lg, bit_depth, ptr(rng), ptr(gmvp), ptr(mvi),
                                     c["bi"], c["faststep"], c["lambda_mv"], 2, 0, c["mot_other"], c["msr"], gop, poc, ref_poc, ptr(mn), ptr(mx),
                                     c["beststep_in"], out)
     return cost, out[0], out[1], out[2], out[3]
@@ -54,7 +54,7 @@ def test_me_ipel_diamond_matches_reference(bi, textured):
         assert max(steps) >= 4  # the diamond rings were actually exercised
 
 
-def run_ref_spel(c):
+def run_ref_spel(c, bit_depth=10):
     from _libs import ref_spel
 
     R = ref_spel()
@@ -62,7 +62,7 @@ def run_ref_spel(c):
     out = (C.c_int * 3)()
     gmvp, mvi = np.array(c["gmvp"], np.int16), np.array(c["mvi"], np.int16)
     cost = R.refdrv_me_spel_pattern(ptr(c["org"], PAD * c["s"] + PAD), c["s"], ptr(c["org_bi"]), ptr(c["ref"], PAD * c["s"] + PAD), c["s"], c["x"], c["y"],
-                                    lg, lg, 10, ptr(gmvp), ptr(mvi), c["bi"], c["lambda_mv"], 2, 0, c["mot_other"], c["hpel_cnt"], c["qpel_cnt"], out)
+                                    lg, lg, bit_depth, ptr(gmvp), ptr(mvi), c["bi"], c["lambda_mv"], 2, 0, c["mot_other"], c["hpel_cnt"], c["qpel_cnt"], out)
     return cost, out[0], out[1], out[2]
 
 
@@ -139,3 +139,73 @@ def test_epzs_with_raster_search_and_integer_refinement_matches_reference():
         c0 = dict(c, raster=0)
         rastered += c["raster"] and bi == 0 and run_oracle_epzs(c0, with_mot=True) != got
     assert rastered > 10 and refined > 30, (rastered, refined)
+
+
+# ---- degenerate content: the oracle must break ties and clip windows as xeve_pinter.c does, or HIP == oracle proves nothing there ------------------------------------
+from _me_cases import EPZS_VARIANTS, GOLDEN_SETS, degenerate_golden_jobs, epzs_variant_of, make_degenerate_jobs, spel_case_of  # noqa: E402
+
+
+def run_ref_epzs(c, bit_depth=10):
+    """(cost, mv x, mv y, pi->mot_bits[lidx]) of the reference's pinter_me_epzs; c["raster"]: me_complexity 2, c["refi"]: the raster step's factor"""
+    R = ref_me()
+    R.refdrv_me_epzs_x.restype = C.c_uint32
+    R.refdrv_me_epzs_x.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, C.c_uint32] + [c_int] * 7 + \
+                                  [c_void_p, c_void_p, c_int, c_int, c_int]
+    R.refdrv_me_epzs_mot_bits.restype = C.c_int
+    lg = c["S"].bit_length() - 1
+    mvp, mv = np.array(c["mvp"], np.int16), np.array(c["mv0"], np.int16)
+    mn, mx = np.array(c["min_clip"], np.int32), np.array(c["max_clip"], np.int32)
+    cost = R.refdrv_me_epzs_x(ptr(c["org"], PAD * c["s"] + PAD), c["s"], ptr(c["org_bi"]), ptr(c["ref"], PAD * c["s"] + PAD), c["s"], c["x"], c["y"], lg, lg, bit_depth,
+                              ptr(mvp), ptr(mv), c["bi"], c["lambda_mv"], 2, c.get("refi", 0), c["mot_other"], c["msr"], c["msr"], c["sr"], 0, ptr(mn), ptr(mx), c["hpel_cnt"],
+                              c["qpel_cnt"], 2 if c.get("raster", 0) else 1)
+    return cost, int(mv[0]), int(mv[1]), R.refdrv_me_epzs_mot_bits()
+
+
+@pytest.mark.parametrize("key", [g[0] for g in GOLDEN_SETS])
+def test_searches_match_reference_where_candidates_tie_and_windows_clip(key):
+    """flat, periodic, outward and static content at every S and bi (the rows of tests/golden/me_degenerate_v1.npz) and 20 further jobs per S and bi: me_ipel_diamond (bi 0, 1, 2),
+    me_spel_pattern with all 8 + 8 points around an integer-pel predictor, pinter_me_epzs plain, with the raster search (refi 0 / 1) and with the integer refinement; the
+    sets *_bd8 / *_bd12 at bit depth 8 and 12 (the SAD loses bit_depth - 8 bits: more ties)"""
+    from _me_cases import run_oracle_epzs, run_oracle_spel
+
+    _, family, bd, kind = GOLDEN_SETS[[g[0] for g in GOLDEN_SETS].index(key)]
+    pl, _, cases = degenerate_golden_jobs(key)
+    r = np.random.default_rng(7300 + len(key) + bd)
+    for S in (8, 16, 32, 64):
+        for bi in (0, 1, 2):
+            cases += make_degenerate_jobs(r, family, S, bi, 20, bd, vertical=bool((S.bit_length() + bi) % 2), static_kind=kind)[1]
+    rastered = 0
+    for it, c in enumerate(cases):
+        cost, mvx, mvy, beststep, mot = run_ref(c, bd)
+        res = run_oracle(c, bd)
+        assert (res.cost, res.mv[0], res.mv[1], res.beststep) == (cost, mvx, mvy, beststep), (key, it, c["S"], c["bi"], c["x"], c["y"])
+        if c["bi"] != 1 and res.best_mv_bits > 0:
+            assert mot == res.best_mv_bits, (key, it)
+        sc = spel_case_of(c)
+        cost, mvx, mvy, mot = run_ref_spel(sc, bd)
+        res = run_oracle_spel(sc, bd)
+        assert (res.cost, res.mv[0], res.mv[1]) == (cost, mvx, mvy), (key, it, "spel", c["S"], c["bi"])
+        if not sc["bi"] and res.best_mv_bits > 0:
+            assert mot == res.best_mv_bits, (key, it, "spel")
+        for v in EPZS_VARIANTS:
+            ec = epzs_variant_of(c, v)
+            got = run_oracle_epzs(ec, with_mot=True, bit_depth=bd)
+            assert got == run_ref_epzs(ec, bd), (key, it, "epzs", v, c["S"], c["bi"])
+            rastered += bool(v[0] and not ec["bi"] and got != run_oracle_epzs(dict(ec, raster=0), with_mot=True, bit_depth=bd))
+    # (the raster search runs when the first search ended beyond step 5: never on flat content, where all SADs are equal and the dense round wins; always on periodic16 / 32,
+    # whose first search ends at step 8 / 16 -- there its grid of step S / 2 sees one SAD at every point from S = 32 on, 81 points for refi 0, but cannot beat the exact match)
+    print(key, "raster search changed the result of", rastered, "jobs")
+    if family == "outward" and bd == 10:
+        assert rastered > 0
+
+
+def test_degenerate_fixture_holds_what_the_reference_gives():
+    """tests/golden/me_degenerate_v1.npz (what the GPU suite holds the device code to, where there is no reference) against the reference itself"""
+    from _me_golden import golden_degenerate_cases
+
+    n = 0
+    for key, bd, c, dia, sp, ep in golden_degenerate_cases():
+        assert run_ref(c, bd)[:4] == dia and run_ref_spel(spel_case_of(c), bd)[:3] == sp, (key, n)
+        assert [run_ref_epzs(epzs_variant_of(c, v), bd) for v in EPZS_VARIANTS] == ep, (key, n)
+        n += 1
+    assert n == 24 * len(GOLDEN_SETS)

@@ -67,7 +67,7 @@ def test_walk_i_pictures_with_count_only_states(case):
 
 
 # ---- P / B slices ------------------------------------------------------------------------------------------------------------------------------------------------
-from _tree_cases import INTER_CASES, make_inter_case, run_oracle_inter_picture  # noqa: E402
+from _tree_cases import DEGENERATE_INTER_CASES, INTER_CASES, make_inter_case, run_oracle_inter_picture  # noqa: E402
 
 
 def run_walk_inter_case(c, full=1, threads=1):
@@ -118,9 +118,15 @@ def check_inter(case, threads=1):
         assert np.array_equal(final[f].reshape(c["maps"][f].shape), c["maps"][f]), (case, "map", f)
 
 
-@pytest.mark.parametrize("case", INTER_CASES, ids=[str(c[0]) for c in INTER_CASES])
+@pytest.mark.parametrize("case", INTER_CASES + DEGENERATE_INTER_CASES, ids=[str(c[0]) for c in INTER_CASES + DEGENERATE_INTER_CASES])
 def test_walk_p_and_b_pictures_match_oracle(case):
+    """(49xx: flat and periodic pictures with identical reference pictures -- walk_inter.h's searches where candidates, reference indices, lists and uni against bi tie)"""
     check_inter(case)
+
+
+def test_walk_periodic_p_picture_with_a_team_of_real_threads():
+    """case 4902 (periodic content, one reference picture) with the team as 64 real threads: the lane-parallel minimum of walk_inter.h must keep the first of equal candidates"""
+    check_inter(DEGENERATE_INTER_CASES[1], threads=64)
 
 
 # ---- the device's team as REAL threads, sync() a barrier: the lane mapping of every stage as the kernel runs it (64 lanes = one wave by default; XEVE_RACE_TESTS=1: the whole

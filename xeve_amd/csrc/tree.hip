@@ -31,6 +31,7 @@ typedef xeve_hip_sbac     SbacState;
 
 struct Node { // one per (level, chain)
     int    active, x0, y0, leaf, do_split, best_split, dist_cu, cu_mode, try_intra, next_split; // next_split: a side node's early-termination verdict (op_leaf_side -> op_exit)
+    int    cu_in_temp; // the node's own CU is what xeve_mode.c would still hold in cu_data_temp of this size (no split alternative was set up after it): op_exit -> cut_node_stale
     double cost_best, cost_temp, unit_cost, cost_split;                                         // cost_split: a side node's split alternative (cost_temp is then the unsplit one's alone)
 };
 
@@ -404,6 +405,17 @@ __device__ static int leaf_next_split(const TreeK &K, const Node *nd, int L)
     return next_split;
 }
 
+// A node the picture cuts has no CU of its own and copies only its quadrants inside the picture into cu_data_temp; the other quadrants keep what the previous node of this
+// size left there, and go out with the CTU's data.  In xeve_mode.c that is the previous node's own CU where no split alternative followed it (:2116-2137: the CU goes
+// through cu_data_temp; an early termination, :2162-2187, or the smallest size leave it there).  This walk stages a node's CU straight into cu_data_best, so it is put
+// into the split alternative's block here, where it shows.
+__device__ static void cut_node_stale(const TreeK &K, int c, int L, CtuData *t)
+{
+    const int log2 = L + 2;
+    cud_copy(t, AT(K.best, L), 0, 0, log2, log2, 2 * (K.log2_ctu - log2), K.idc, K.ws, K.hs);
+    __syncthreads();
+}
+
 __device__ static void op_leaf(const TreeK &K, int c, int L, int *sh)
 {
     const xeve_hip_ctu_job J = K.jobs[c];
@@ -420,11 +432,12 @@ __device__ static void op_leaf(const TreeK &K, int c, int L, int *sh)
             nd->cost_temp = (double)(int)split_flag_bits(*AT(K.before, L), run, 1) * K.lambda0;
             *AT(K.curr, L) = run, *AT(K.csplit, L) = run;
         }
-        sh[0] = do_split;
+        sh[0] = do_split, sh[1] = do_split && !nd->leaf && nd->cu_in_temp;
     }
     __syncthreads();
-    const int do_split = sh[0];
+    const int do_split = sh[0], stale_cu = sh[1];
     __syncthreads();
+    if(stale_cu) cut_node_stale(K, c, L, t);
     if(do_split) {
         cud_init(t, log2);
         clear_map(K, J.pic, x0, y0, cu);
@@ -449,11 +462,12 @@ __device__ static void op_split_prep(const TreeK &K, int c, int L, int *sh)
             nd->cost_split = (double)(int)split_flag_bits(*AT(K.before, L), run, 1) * K.lambda0;
             *AT(K.csplit, L) = run;
         }
-        sh[0] = do_split;
+        sh[0] = do_split, sh[1] = do_split && !nd->leaf && nd->cu_in_temp;
     }
     __syncthreads();
-    const int do_split = sh[0];
+    const int do_split = sh[0], stale_cu = sh[1];
     __syncthreads();
+    if(stale_cu) cut_node_stale(K, c, L, AT(K.tsplit, L));
     if(do_split) {
         cud_init(AT(K.tsplit, L), log2);
         clear_map(K, J.pic, nd->x0, nd->y0, cu);
@@ -492,6 +506,7 @@ __device__ static void op_exit(const TreeK &K, int c, int L, int *sh)
         const double cost_split = side ? nd->cost_split : nd->cost_temp;
         sh[0] = nd->do_split && (!side || nd->next_split) && nd->cost_best - 0.0001 > cost_split;
         if(sh[0]) nd->cost_best = cost_split, nd->best_split = 5 /* SPLIT_QUAD */;
+        nd->cu_in_temp = nd->leaf && !(nd->do_split && (!side || nd->next_split));
     }
     __syncthreads();
     const int split_wins = sh[0];
