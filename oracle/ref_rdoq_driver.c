@@ -39,3 +39,22 @@ long long refdrv_err_scale(int qp_rem, int log2_size, int bit_depth, int tool_iq
     xeve_init_err_scale(ctx);
     return ctx->err_scale[qp_rem][log2_size - 1];
 }
+
+/* the reference's transform + PLAIN quantiser (xeve_tq_nnz -> xeve_quant_nnz with use_rdoq = 0, xeve_tq.c:704-727: levels stored through (s16) casts) of one luma block,
+ * through the exported xeve_sub_block_tq; coef: the residual in, the levels out (log2w, log2h <= 6).  Returns nnz. */
+int refdrv_tq(s16 *coef, int log2w, int log2h, int qp, int slice_type, int bit_depth)
+{
+    static XEVE_CTX  *ctx;
+    static XEVE_CORE *core;
+    static s16 (*buf)[MAX_CU_DIM];
+    int nnz[N_C] = {0};
+    if(!ctx) ctx = calloc(1, sizeof(*ctx)), core = calloc(1, sizeof(*core)), buf = calloc(N_C, sizeof(*buf));
+    xeve_func_txb = &xeve_tbl_txb;
+    ctx->param.tool_iqt = 0, ctx->param.codec_bit_depth = bit_depth, ctx->param.rdoq = 0, ctx->param.cs_w_shift = ctx->param.cs_h_shift = 1;
+    ctx->sps.bit_depth_luma_minus8 = ctx->sps.bit_depth_chroma_minus8 = bit_depth - 8, ctx->sps.chroma_format_idc = 1;
+    core->ctx = ctx, core->qp_y = core->qp_u = core->qp_v = (u8)qp;
+    memcpy(buf[0], coef, sizeof(s16) << (log2w + log2h));
+    xeve_sub_block_tq(ctx, core, buf, log2w, log2h, slice_type, nnz, 0, 1 /* luma only */);
+    memcpy(coef, buf[0], sizeof(s16) << (log2w + log2h));
+    return nnz[0];
+}

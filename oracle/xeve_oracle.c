@@ -925,7 +925,7 @@ int xo_rdoq(int16_t *coef, int log2w, int log2h, int qp, double d_lambda, int is
         if(!((level_double - ((int64_t)m << q_bits)) < ((int64_t)1 << (q_bits - 1)))) m++;
         const int64_t err = (level_double * es) >> 20;
         block_uncoded += err * err;
-        ld[p] = level_double, mx[p] = v > 0 ? (int16_t)m : -(int16_t)m;
+        ld[p] = level_double, mx[p] = (int16_t)(v > 0 ? (int16_t)m : -(int16_t)m); /* tmp_coef is an s16: a level of 32768 is -32768 under either sign */
         sum_all += (int)m;
     }
     if(sum_all != 0) {

@@ -66,13 +66,44 @@ REAL_CASES = {
 }
 
 
+def _saturated(w, h, frames, seed):
+    """content whose every sample is 0 or 255 -- full-scale residuals, saturated edges, the reconstruction's clip under ringing:
+    9300 + k: i.i.d. binary noise (the densest content found for the slice buffers, enc_plan.h slice_capacity);
+    9400 + k: binary cells of 32x32 luma / 16x16 chroma samples, the grid drifting by (+8, +4) luma samples per frame -- flat full-scale residuals on 32- and 64-point
+              blocks, saturated edges inside CUs;
+    9500 + k: a one-sample checkerboard whose phase flips every frame -- one coefficient at full scale, the zero vector the worst candidate, +-1 exact ties;
+    9600 + k: a scene cut, frame 0 flat 0 and every later frame flat 255 -- the inter residual of 1020 (10-bit) over whole 64x64 CUs"""
+    import numpy as np
+
+    kind, r = (seed - 9300) // 100, np.random.default_rng(seed)
+    planes = ((w, h, 1), (w // 2, h // 2, 2), (w // 2, h // 2, 2))
+    if kind == 0:
+        return (r.integers(0, 2, size=w * h * 3 // 2 * frames, dtype=np.uint8) * 255).astype(np.uint8)
+    grids = [r.integers(0, 2, size=(64, 64), dtype=np.uint8) for _ in planes]  # (cells: one grid per plane, indexed modulo 64 cells)
+    out = []
+    for t in range(frames):
+        for (pw, ph, sc), g in zip(planes, grids):
+            yy, xx = np.mgrid[0:ph, 0:pw]
+            if kind == 1:
+                a = g[((yy * sc + 4 * t) // 32) % 64, ((xx * sc + 8 * t) // 32) % 64]
+            elif kind == 2:
+                a = (xx + yy + t) & 1
+            else:
+                a = np.full((ph, pw), 1 if t else 0)
+            out.append((a * 255).astype(np.uint8).reshape(-1))
+    return np.concatenate(out)
+
+
 def make_yuv(path, w, h, frames, seed):
     """seeds below 5000: i.i.d. noise (SURVEY.md 8d recipe); from 5000: a smooth texture drifting over the frames plus light noise -- content on
-    which skip / merge, temporal direct and bi-prediction actually win; 9000 .. 9255: every sample of every plane = seed - 9000 (saturated content: flat 0, flat 255)"""
+    which skip / merge, temporal direct and bi-prediction actually win; 9000 .. 9255: every sample of every plane = seed - 9000 (saturated content: flat 0, flat 255); 9300 .. 9699: 0 / 255 content (_saturated)"""
     import numpy as np
 
     if 9000 <= seed <= 9255:
         np.full(w * h * 3 // 2 * frames, seed - 9000, dtype=np.uint8).tofile(path)
+        return
+    if 9300 <= seed < 9700:
+        _saturated(w, h, frames, seed).tofile(path)
         return
     random.seed(seed)
     if seed < 5000:  # bytes(random.getrandbits(8) ...) without the Python loop: getrandbits(8) is the top byte of one MT19937 output, and numpy's legacy generator runs

@@ -234,6 +234,36 @@ QP_RANGE_CASES = {
     "q0_flat255": (128, 64, 1, 3, 9255, ["--preset", "medium", "-b", "1", "-q", "0"], 1),
     "q51_flat0": (128, 64, 1, 3, 9000, ["--preset", "medium", "-b", "1", "-q", "51"], 1),
 }
+# Saturated content (tests/_e2e.py _saturated: every sample 0 or 255 -- binary noise 9300 + k, drifting 32x32 cells 9400 + k, the flipping one-sample checkerboard
+# 9500 + k, the scene cut 9600 + k), all at 128x64 unless said: large flat residuals, full-scale edges and single coefficients through the residual path down to the QPs
+# at which the reference's 16-bit levels wrap (64-point blocks below QP 10, 32-point blocks below QP 4), slice data above the rate of uniform noise (slice_capacity).
+_LDB = ["--preset", "fast", "-I", "0", "-b", "0"]
+SATURATED_CASES = {
+    "sat_noise_q0_ldb": (128, 64, 1, 2, 9301, _LDB + ["-q", "0"], 1),
+    "sat_noise_q12_closed": (128, 64, 1, 4, 9301, ["--preset", "medium", "--closed-gop", "-I", "4", "-b", "3", "-q", "12"], 1),
+    "sat_noise_q24_ra": (128, 64, 1, 3, 9301, ["--preset", "medium", "-b", "1", "-q", "24"], 1),
+    "sat_noise_q12_10bit": (128, 64, 1, 2, 9301, _LDB + ["-q", "12", "-d", "10"], 1),
+    "sat_noise_q12_m2": (128, 128, 1, 2, 9301, _LDB + ["-q", "12"], 2),  # two row chains, the second writer pass
+    "sat_cells_q1_ldb": (128, 64, 1, 3, 9401, _LDB + ["-q", "1"], 1),
+    "sat_cells_q8_closed": (128, 64, 1, 4, 9401, ["--preset", "medium", "--closed-gop", "-I", "4", "-b", "3", "-q", "8"], 1),
+    "sat_cells_q32_ra": (128, 64, 1, 3, 9401, ["--preset", "medium", "-b", "1", "-q", "32"], 1),
+    "sat_checker_q0_ldb": (128, 64, 1, 3, 9501, _LDB + ["-q", "0"], 1),
+    "sat_checker_q27_b3": (128, 64, 1, 5, 9501, ["--preset", "medium", "-b", "3", "-q", "27"], 1),
+    "sat_cut_q1_ldb": (128, 64, 1, 2, 9601, _LDB + ["-q", "1"], 1),
+    "sat_cut_q9_ldb": (128, 64, 1, 2, 9601, _LDB + ["-q", "9"], 1),
+    "sat_cut_q30_ldb": (128, 64, 1, 2, 9601, _LDB + ["-q", "30"], 1),
+    # presets slow and placebo (the fused walk only; placebo: 64x64 intra CUs, 4x4 inter CUs)
+    "sat_cells_q1_slow": (128, 64, 1, 3, 9401, ["--preset", "slow", "-I", "0", "-b", "0", "-q", "1"], 1),
+    "sat_cells_q1_placebo": (128, 64, 1, 3, 9401, ["--preset", "placebo", "-I", "0", "-b", "0", "-q", "1"], 1),
+}
+# the default GPU suite's share (the others, the fused walk's run of sat_noise_q0_ldb among them, carry gpu_full); sat_checker_q0_ldb and sat_cells_q1_placebo left it too,
+# in the order the 900 s of tests/test_gpu_suite_budget.py ask for: the one full run that held them all took 916 s
+SATURATED_GPU_DEFAULT = ("sat_noise_q0_ldb", "sat_cells_q1_ldb", "sat_cut_q1_ldb", "sat_cells_q1_slow")
+# the same at 1920x1080, two frames (GPU suite with gpu_full only)
+SATURATED_REAL_CASES = {
+    "sat_noise_q24_1080p": (1920, 1080, 1, 2, 9301, _LDB + ["-q", "24"], 8),
+    "sat_cells_q1_1080p_m8": (1920, 1080, 1, 2, 9401, _LDB + ["-q", "1"], 8),
+}
 # Picture sizes modulo the 64-sample CTU (Param::finish takes every positive multiple of 8 from 8x8 up): pictures smaller than one CTU in one or both directions, one CU
 # row / one CU column, and partial last CTU columns and rows of every remainder 8 .. 56 -- each remainder once at the right edge and once at the bottom edge.  The search
 # range (32 / 64 / 128 / 384) is larger than most of these pictures, and so is the padding (144 / 72).  A = closed GOP of I + three B pictures, B = low delay.
@@ -310,11 +340,11 @@ def widen10(data8):
     return ((b << 2) | ((b * 3 + np.arange(b.size, dtype=np.uint16)) & 3)).astype("<u2").tobytes()
 
 
-def qp_range_input(yuv_dir, name):
-    """the input of a QP_RANGE_CASES entry as the encoders take it: one bytes object per GOP (16-bit samples where the options say -d 10)"""
+def qp_range_input(yuv_dir, name, cases=None):
+    """the input of a QP_RANGE_CASES entry (or of an entry of `cases`) as the encoders take it: one bytes object per GOP (16-bit samples where the options say -d 10)"""
     import _e2e
 
-    w, h, gops, frames, seed, cli, _ = QP_RANGE_CASES[name]
+    w, h, gops, frames, seed, cli, _ = (cases or QP_RANGE_CASES)[name]
     p = os.path.join(yuv_dir, name + ".yuv")
     if not os.path.exists(p):
         _e2e.make_yuv(p, w, h, gops * frames, seed)

@@ -286,6 +286,9 @@ def ref_rdoq():
         L.refdrv_scan.argtypes = [c_int, c_int]
         L.refdrv_err_scale.restype = C.c_longlong
         L.refdrv_err_scale.argtypes = [c_int] * 4
+        if hasattr(L, "refdrv_tq"):  # (transform + plain quantiser through xeve_sub_block_tq)
+            L.refdrv_tq.restype = c_int
+            L.refdrv_tq.argtypes = [c_void_p] + [c_int] * 5
         _ref_rdoq = L
     return _ref_rdoq
 

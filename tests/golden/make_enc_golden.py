@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Writes tests/golden/enc_v1.json from the UNMODIFIED reference application (oracle/_ref/xeveb_app).  Build container only.
   "plans":   per (options, frames) the table the application prints per coded picture -- POC, temporal id, slice type, QP, first reference picture of each list;
-  "batches": per case of tests/_enc.py BATCH_CASES(_REAL) (and the lists behind them, QP_RANGE_CASES and PICTURE_SIZE_CASES included) the md5 + size of every GOP's bitstream, each GOP coded as a run of its own (--seek g * F --frames F).
+  "batches": per case of tests/_enc.py BATCH_CASES(_REAL) (and the lists behind them, QP_RANGE_CASES, PICTURE_SIZE_CASES and SATURATED_CASES included) the md5 + size of every GOP's bitstream, each GOP coded as a run of its own (--seek g * F --frames F).
 usage: make_enc_golden.py [plans] [case names ...] -- without arguments everything is (re)made."""
 import json
 import os
@@ -12,7 +12,7 @@ import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from _e2e import make_yuv  # noqa: E402
-from _enc import BATCH_CASES, BATCH_CASES_REAL, DEPTH10_CASES, GOLDEN, HEADER_OPTION_CASES, HOST_PINNED_CASES, PLACEBO_BATCH_CASES, PICTURE_SIZE_CASES, PICTURE_SIZE_HOST_CASES, PLAN_GRID, PRESET_REAL_CASES, QP_RANGE_CASES, SLOW_BATCH_CASES, WIDE_STACK_CASES, app_args_and_env, md5, widen10  # noqa: E402
+from _enc import BATCH_CASES, BATCH_CASES_REAL, DEPTH10_CASES, GOLDEN, HEADER_OPTION_CASES, HOST_PINNED_CASES, PLACEBO_BATCH_CASES, PICTURE_SIZE_CASES, PICTURE_SIZE_HOST_CASES, PLAN_GRID, PRESET_REAL_CASES, QP_RANGE_CASES, SATURATED_CASES, SATURATED_REAL_CASES, SLOW_BATCH_CASES, WIDE_STACK_CASES, app_args_and_env, md5, widen10  # noqa: E402
 from _libs import REF_APP  # noqa: E402
 
 ROW = re.compile(r"^(?:\[.*?\] )*(\d+)\s+(\d+)\s+\((.)\)\s+(\d+)\s+[\d.]+\s+[\d.]+\s+[\d.]+\s+\d+\s+\d+\s*(.*)$")
@@ -26,6 +26,17 @@ def app(yuv, out, w, h, frames, cli, threads, seek=0):
     p = subprocess.run(cmd, capture_output=True, text=True, env=dict(os.environ, **pin))
     assert p.returncode == 0, (cmd, p.stdout[-1500:], p.stderr[-2000:])
     return p.stdout
+
+
+def slice_data_bytes(stream):
+    out, pos = [], 0
+    while pos < len(stream):  # the application's output: a 4-byte big-endian length in front of every NAL unit
+        n = int.from_bytes(stream[pos:pos + 4], "big")
+        nal = stream[pos + 4:pos + 4 + n]
+        if ((nal[0] >> 1) & 0x3F) - 1 in (0, 1):  # nal_unit_type_plus1: non-IDR and IDR slices
+            out.append(len(nal.rstrip(b"\0")))
+        pos += 4 + n
+    return out
 
 
 only = sys.argv[1:]
@@ -46,7 +57,7 @@ with tempfile.TemporaryDirectory() as d:
                 assert len(rows) == n, (cli, n, rows)
                 out["plans"].append({"cli": cli, "frames": n, "rows": rows})
         print("plans:", len(out["plans"]))
-    for name, (w, h, gops, frames, seed, cli, threads) in list(BATCH_CASES.items()) + list(BATCH_CASES_REAL.items()) + list(DEPTH10_CASES.items()) + list(HOST_PINNED_CASES.items()) + list(HEADER_OPTION_CASES.items()) + list(SLOW_BATCH_CASES.items()) + list(PLACEBO_BATCH_CASES.items()) + list(PRESET_REAL_CASES.items()) + list(QP_RANGE_CASES.items()) + list(WIDE_STACK_CASES.items()) + list(PICTURE_SIZE_CASES.items()) + list(PICTURE_SIZE_HOST_CASES.items()):
+    for name, (w, h, gops, frames, seed, cli, threads) in list(BATCH_CASES.items()) + list(BATCH_CASES_REAL.items()) + list(DEPTH10_CASES.items()) + list(HOST_PINNED_CASES.items()) + list(HEADER_OPTION_CASES.items()) + list(SLOW_BATCH_CASES.items()) + list(PLACEBO_BATCH_CASES.items()) + list(PRESET_REAL_CASES.items()) + list(QP_RANGE_CASES.items()) + list(WIDE_STACK_CASES.items()) + list(PICTURE_SIZE_CASES.items()) + list(PICTURE_SIZE_HOST_CASES.items()) + list(SATURATED_CASES.items()) + list(SATURATED_REAL_CASES.items()):
         if only and name not in only:
             continue
         yuv, evc = os.path.join(d, name + ".yuv"), os.path.join(d, name + ".evc")
@@ -60,6 +71,8 @@ with tempfile.TemporaryDirectory() as d:
             app(yuv, evc, w, h, frames, cli, threads, seek=g * frames)
             b = open(evc, "rb").read()
             per.append({"md5": md5(b), "bytes": len(b)})
+            if name in SATURATED_CASES:  # each slice NAL unit without the cabac_zero_words behind its slice data: what the device's writers put into a picture's buffer
+                per[-1]["slice_data_bytes"] = slice_data_bytes(b)
         out["batches"][name] = {"w": w, "h": h, "gops": gops, "frames": frames, "seed": seed, "cli": cli, "threads": threads, "per_gop": per}
         if gops > 1 and (name in BATCH_CASES or name in DEPTH10_CASES or name in HOST_PINNED_CASES or name in HEADER_OPTION_CASES or name in SLOW_BATCH_CASES or name in PLACEBO_BATCH_CASES or name in QP_RANGE_CASES or name in PICTURE_SIZE_CASES):  # the whole sequence in ONE run of the reference: what the concatenated per-GOP bitstreams must be
             app(yuv, evc, w, h, gops * frames, cli, threads)

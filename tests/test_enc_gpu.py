@@ -143,6 +143,36 @@ def test_the_ends_of_the_qp_range_on_the_gpu(name, walk, hip, yuv_dir):
     assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in g["per_gop"]]
 
 
+def _saturated_params():
+    """as _qp_range_params; the cases outside _enc.SATURATED_GPU_DEFAULT carry gpu_full"""
+    out = []
+    for n in sorted(_enc.SATURATED_CASES):
+        fused_only = _enc.SATURATED_CASES[n][5][1] in ("slow", "placebo")
+        for w in ((1,) if fused_only else (0, 1)):
+            full = n not in _enc.SATURATED_GPU_DEFAULT or (n, w) == ("sat_noise_q0_ldb", 1)  # (4.7 s: the first case to leave the default suite for its 900 s)
+            out.append(pytest.param(n, w, id="%s-%s" % (n, WALK_NAME[w]), marks=(pytest.mark.gpu_full,) if full else ()))
+    return out
+
+
+def _saturated_run(hip, cases, name, walk, yuv_dir):
+    w, h, gops, frames, seed, cli, threads = cases[name]
+    c = _enc.config(w, h, cli, threads)
+    cfg = hip.config(w, h, qp=c.qp, keyint=c.keyint, bframes=c.bframes, closed_gop=c.closed_gop, preset=c.preset, threads=c.threads, ref=c.ref, input_depth=c.reserved[1] or 8)
+    with hip.walk_select(walk):
+        outs, st = _run(hip, cfg, _enc.qp_range_input(yuv_dir, name, cases), frames)
+    return outs, st
+
+
+@pytest.mark.parametrize("name,walk", _saturated_params())
+def test_saturated_content_on_the_gpu(name, walk, hip, yuv_dir):
+    """pictures whose every sample is 0 or 255 (tests/_e2e.py: binary noise, drifting 32x32 cells, the flipping one-sample checkerboard, the scene cut) at QPs down to 0
+    through the device path: full-scale flat residuals on 32- and 64-point blocks where the reference's (s16) levels wrap, the matrix-core transforms at full scale, the
+    walk's quantiser / RDOQ and its packed run / level entries, unary level strings tens of thousands of bins long, the reconstruction's clip under ringing, slice data
+    1.25 .. 2.2 times that of uniform noise (enc_plan.h slice_capacity): every GOP = the unmodified reference's bytes (tests/golden/enc_v1.json), no harness between"""
+    outs, _ = _saturated_run(hip, _enc.SATURATED_CASES, name, walk, yuv_dir)
+    assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in _enc.golden()["batches"][name]["per_gop"]]
+
+
 SIZE_FUSED = ("size_8x8_noise", "size_24x40_moving", "size_104x112_noise", "size_176x144_noise_m2")  # the fused walk's device build at four of the shapes its host side is held at
 
 
@@ -280,6 +310,44 @@ def test_a_batch_is_the_same_as_its_gops_coded_alone(hip, yuv_dir):
     assert _enc.md5(alone[0]) == _enc.golden()["batches"]["gops_128x64_noise"]["per_gop"][1]["md5"]
 
 
+@pytest.mark.parametrize("shape", ["first_pass", "second_pass", "second_pass_two_chains"])
+def test_a_picture_that_outgrows_its_slice_buffer_ends_the_run_with_an_error(shape, hip, yuv_dir, monkeypatch):
+    """the engine's handling of an overflow (the writers' own bounds checks: tests/test_eco_lane.py, tests/test_hip_tree.py).  Binary noise at -q 12 with the writer kernels
+    and the fetch TOLD a buffer of half the slice data of the golden's largest picture (XEVE_HIP_ENC_SLICE_TOLD, read at create; the allocation stays slice_capacity(),
+    so a defective bounds check shows here as a failed assertion, not as a fault): the run ends with the error and no GOP has a byte of bitstream -- on one chain (the
+    first-pass writer appends the slice data), through the second writer pass at 128x64 (one CTU row: one chain), and with two row chains at 128x128.  A fresh encoder of
+    the same process is untouched.  The slice data is the slice NAL unit WITHOUT the cabac_zero_words the host appends: 12 279 of the I picture's 38 555 bytes here, so
+    half of the NAL unit's size would still hold every picture."""
+    import xeve_amd
+
+    name = "sat_noise_q12_m2" if shape == "second_pass_two_chains" else "sat_noise_q12_closed"
+    sizes = _enc.golden()["batches"][name]["per_gop"][0]["slice_data_bytes"]
+    told = max(sizes) // 2
+    w, h, gops, frames, seed, cli, threads = _enc.SATURATED_CASES[name]
+    cfg = _cfg(hip, w, h, cli, threads, always_second_pass=shape == "second_pass")
+    assert len(sizes) == frames and 0 < told < min(sizes) and max(sizes) < hip.slice_capacity(cfg, frames)  # (every picture outgrows it; none outgrows the allocation)
+    monkeypatch.setenv("XEVE_HIP_ENC_SLICE_TOLD", str(hip.slice_capacity(cfg, frames) + 1))
+    with pytest.raises(xeve_amd.XeveHipError, match="XEVE_HIP_ENC_SLICE_TOLD"):  # (above the allocation: refused)
+        hip.BatchEncoder(cfg, 2, frames)
+    monkeypatch.setenv("XEVE_HIP_ENC_SLICE_TOLD", str(told))
+    data = _enc.qp_range_input(yuv_dir, name, _enc.SATURATED_CASES)[0]
+    enc = hip.BatchEncoder(cfg, 2, frames)
+    try:
+        for g in range(2):
+            enc.push_gop(g, data)
+        with pytest.raises(xeve_amd.XeveHipError, match="outgrew"):
+            enc.encode()
+        assert enc.bitstream_sizes() == [0, 0]
+    finally:
+        enc.close()
+    monkeypatch.delenv("XEVE_HIP_ENC_SLICE_TOLD")
+    w, h, gops, frames, seed, cli, threads = _enc.BATCH_CASES["gops_128x64_noise"]
+    gold = _enc.golden()["batches"]["gops_128x64_noise"]["per_gop"]
+    data, fb = _frames(yuv_dir, "gops_128x64_noise", w, h, gops * frames, seed), w * h * 3 // 2 * frames
+    outs, _ = _run(hip, _cfg(hip, w, h, cli, threads), [data[i * fb:(i + 1) * fb] for i in range(gops)], frames)
+    assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in gold]
+
+
 def test_a_wide_batch_fed_from_device_memory_keeps_every_gop_exact(hip, yuv_dir):
     """288 GOPs in lockstep (96 copies of the three GOPs of the noise case), the frames pushed as device tensors that torch is still producing on its own stream when
     push is called: GOP i of the batch = the reference's bytes of GOP i % 3, at both ends of the batch and everywhere between"""
@@ -335,6 +403,17 @@ def test_presets_slow_and_placebo_at_1920x1080_on_the_gpu(name, hip, yuv_dir):
     outs, st = _run(hip, _cfg(hip, w, h, cli, threads), [data[i * fb:(i + 1) * fb] for i in range(gops)], frames)
     print(name, st)
     assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in g["per_gop"]]
+
+
+@pytest.mark.gpu_last
+@pytest.mark.gpu_full
+@pytest.mark.parametrize("name", sorted(_enc.SATURATED_REAL_CASES))
+def test_saturated_content_at_1920x1080_on_the_gpu(name, hip, yuv_dir):
+    """binary noise at -q 24 (0.94 bytes per sample: above what the slice buffers held before they were sized for it) and the 32x32 cells at -q 1 (the wrap zone of the
+    64- and 32-point blocks), two low-delay pictures at 1920x1080 with 8 row chains, on the library's own choice of walk = the reference application's bitstreams"""
+    outs, st = _saturated_run(hip, _enc.SATURATED_REAL_CASES, name, -1, yuv_dir)
+    print(name, st)
+    assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in _enc.golden()["batches"][name]["per_gop"]]
 
 
 # BASELINE's configs at their real picture sizes (gpu_last: after every other GPU test).  The default suite has to fit the driver's 1200 s on one MI355X (tests/conftest.py),

@@ -113,6 +113,17 @@ def test_the_ends_of_the_qp_range_on_the_host_side(name, yuv_dir):
         assert (len(whole), _enc.md5(whole)) == (g["whole"]["bytes"], g["whole"]["md5"])
 
 
+@pytest.mark.parametrize("name", sorted(_enc.SATURATED_CASES))
+def test_saturated_content_on_the_host_side(name, yuv_dir):
+    """pictures whose every sample is 0 or 255 (tests/_e2e.py: binary noise, drifting 32x32 cells, the flipping checkerboard, the scene cut) at QPs down to 0: full-scale
+    flat residuals on 32- and 64-point blocks where the reference's (s16) levels wrap (xeve_tq.c: 64-point blocks below QP 10, 32-point blocks below QP 4), unary level
+    strings tens of thousands of bins long, the reconstruction's clip under ringing, slice data above the rate of uniform noise -- every GOP = the unmodified reference's run"""
+    w, h, gops, frames, seed, cli, threads = _enc.SATURATED_CASES[name]
+    g = _enc.golden()["batches"][name]
+    outs = _enc.encode_cpu(_enc.config(w, h, cli, threads), _enc.qp_range_input(yuv_dir, name, _enc.SATURATED_CASES), frames)
+    assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in g["per_gop"]]
+
+
 SIZE_CASES = dict(_enc.PICTURE_SIZE_CASES, **_enc.PICTURE_SIZE_HOST_CASES)
 
 

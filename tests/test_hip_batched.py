@@ -668,3 +668,123 @@ def test_fused_mc_distortion_at_far_offsets_vs_oracle(dev, far, luma):
             assert ssd[i] == O.xo_ssd(w, h, ptr(blocks[P]), ptr(e), w, w, 10), (luma, w, P, i)
             if luma:
                 assert sad[i] == O.xo_sad(w, h, ptr(blocks[P]), ptr(e), w, w, 10), (w, P, i)
+
+
+# ---- the 16-bit wrap zone: full-scale residuals at QP 1, 3, 4, 9 (tests/_rdoq_cases.py saturated_residuals) -------------------------------------------------------------
+WRAP_QPS = (1, 3, 4, 9)
+WRAP_SIZES = [(4, 4), (5, 5), (6, 6), (4, 5), (6, 5)]  # 16 points: the control (nothing wraps); 32 and 64 points: dct_mfma.hip
+
+
+def _plain_wrap_count(coef_fwd, levels_out, lw, lh, qp, intra):
+    """positions whose plain level is above 32767 before the (s16) cast and whose output IS the wrapped value"""
+    from _rdoq_cases import plain_levels
+
+    lev = plain_levels(coef_fwd, lw, lh, qp, 10, intra)
+    return int(((lev > 32767) & (np.abs(levels_out.astype(np.int64)) == np.abs(lev.astype(np.int16).astype(np.int64)))).sum())
+
+
+@pytest.mark.parametrize("lw,lh", WRAP_SIZES)
+def test_tq_chain_where_16_bit_levels_wrap(dev, lw, lh):
+    """D.trans / D.quant / D.dquant / D.itrans on nine full-scale residual blocks per QP: the reference's plain quantiser stores its level through an (s16) cast
+    (xeve_tq.c:723-724; the oracle is held to it on these blocks by tests/test_oracle_vs_ref.py), so on 32-point blocks at QP 1 and 3 and on 64-point blocks at every QP
+    here the level wraps, and the wrapped level is what is dequantised and inverse-transformed.  Asserted: the wrap happened wherever a full-scale residual gets there."""
+    import torch
+
+    from _rdoq_cases import plain_wraps_expected, saturated_residuals
+    from xeve_amd import device as D
+
+    O = oracle()
+    for qp in WRAP_QPS:
+        resid = saturated_residuals(lw, lh, qp, 10)
+        qs, dqs = D.QUANT_SCALE[0][qp % 6], D.DQ_SCALE[qp % 6] << (qp // 6)
+        for intra in (0, 1):
+            d = torch.from_numpy(resid.copy()).to(dev)
+            D.trans(d, lw, lh, 10)
+            fwd = d.cpu().numpy().copy()
+            nnz = D.quant(d, lw, lh, qp, qs, intra, 10).cpu().numpy()
+            q = d.cpu().numpy().copy()
+            D.dquant(d, lw, lh, dqs, 10)
+            dq = d.cpu().numpy().copy()
+            D.itrans(d, lw, lh, 10)
+            inv = d.cpu().numpy()
+            for b in range(len(resid)):
+                e = resid[b].copy()
+                O.xo_trans(ptr(e), lw, lh, 10)
+                assert np.array_equal(fwd[b], e), ("trans", qp, b)
+                assert nnz[b] == O.xo_quant(ptr(e), lw, lh, qp, qs, intra, 10) and np.array_equal(q[b], e), ("quant", qp, intra, b)
+                O.xo_dquant(ptr(e), lw, lh, dqs, 10)
+                assert np.array_equal(dq[b], e), ("dquant", qp, intra, b)
+                O.xo_itrans(ptr(e), lw, lh, 10)
+                assert np.array_equal(inv[b], e), ("itrans", qp, intra, b)
+            assert (_plain_wrap_count(fwd, q, lw, lh, qp, intra) > 0) == plain_wraps_expected(lw, lh, qp, 10), (lw, lh, qp, intra)
+
+
+@pytest.mark.parametrize("rdoq", [0, 1], ids=["residual_rdo", "residual_rdoq"])
+@pytest.mark.parametrize("lw,lh", WRAP_SIZES)
+def test_fused_residual_chains_where_16_bit_levels_wrap(dev, lw, lh, rdoq):
+    """xeve_hip_residual_rdo and xeve_hip_residual_rdoq (DIFF, SSD, DCT -- the matrix cores at 32 and 64 points --, zero pre-test, quantiser or RDOQ, dequant, IDCT,
+    recon with its clip to 0 .. 1023, SSD) on original / prediction pairs whose difference is a full-scale residual block, QP 1, 3, 4, 9: every output = the oracle's
+    step-by-step chain, and where a level can pass 32767 the coded levels show the wrapped value (RDOQ estimates capped for the reference's s32 rate)"""
+    import ctypes as C
+
+    import torch
+
+    from _libs import oracle_rdoq
+    from _rdoq_cases import cap_est, make_est, plain_wraps_expected, saturated_residuals, unwrapped_levels, wrapped_outputs, wraps_expected
+    from xeve_amd import device as D
+    from xeve_amd import lib
+
+    O, OR = oracle(), oracle_rdoq()
+    w, h, bd = 1 << lw, 1 << lh, 10
+    n, s = w * h, 4 * 64 + 32
+    for qp in WRAP_QPS:
+        resid = saturated_residuals(lw, lh, qp, bd)
+        nblk = len(resid)
+        offs = [(8 + (b // 4) * h) * s + 8 + (b % 4) * w for b in range(nblk)]
+        org = np.full((3 * 64 + 16, s), 512, np.int16)
+        pred = np.where(resid < 0, -resid, 0).astype(np.int16)  # org - pred = the residual, both inside 0 .. 1023
+        for b in range(nblk):
+            y0, x0 = offs[b] // s, offs[b] % s
+            org[y0:y0 + h, x0:x0 + w] = np.where(resid[b] > 0, resid[b], 0).reshape(h, w)
+        fwd = resid.copy()
+        for b in range(nblk):
+            O.xo_trans(ptr(fwd, b * n), lw, lh, bd)
+        est, lam = make_est(np.random.default_rng(4500 + (lw * 8 + lh) * 16 + qp)), 0.57 * 2.0 ** ((qp - 12) / 3.0)
+        levels = unwrapped_levels(fwd, lw, lh, qp, bd)
+        cap_est(est, levels)
+        for intra in (0, 1):
+            d_org, d_pred = torch.from_numpy(org).to(dev), torch.from_numpy(pred).to(dev)
+            jobs = D.make_jobs(offs, np.arange(nblk) * n, dev)
+            coef = torch.full((nblk, n), 77, dtype=torch.int16, device=dev)
+            rec = torch.zeros_like(d_org)
+            nnz = torch.zeros(nblk, dtype=torch.int32, device=dev)
+            ssd = torch.zeros((nblk, 2), dtype=torch.int64, device=dev)
+            if rdoq:
+                D.residual_rdoq(d_org, s, d_pred, w, jobs, lw, lh, bd, qp, intra, lam, 1, lib.RdoqEst.from_buffer_copy(bytes(est)), coef, rec, s, nnz, ssd)
+            else:
+                D.residual_rdo(d_org, s, d_pred, w, jobs, lw, lh, bd, qp, intra, 1, coef, rec, s, nnz, ssd)
+            coef, rec, nnz, ssd = coef.cpu().numpy(), rec.cpu().numpy(), nnz.cpu().numpy(), ssd.cpu().numpy()
+            qs, dqs = D.QUANT_SCALE[0][qp % 6], D.DQ_SCALE[qp % 6] << (qp // 6)
+            for b in range(nblk):
+                c = np.zeros(n, np.int16)
+                O.xo_diff(w, h, ptr(org, offs[b]), ptr(pred, b * n), s, w, w, ptr(c))
+                assert np.array_equal(c, resid[b]) and ssd[b, 0] == O.xo_ssd(w, h, ptr(org, offs[b]), ptr(pred, b * n), s, w, bd)
+                O.xo_trans(ptr(c), lw, lh, bd)
+                if not O.xo_rdoq_zero_test(ptr(c), lw, lh, qp, qs, intra, bd):
+                    c[:], e_nnz = 0, 0
+                elif rdoq:
+                    e_nnz = OR.xo_rdoq(ptr(c), lw, lh, qp, lam, 1, bd, 0, C.byref(est))
+                else:
+                    e_nnz = O.xo_quant(ptr(c), lw, lh, qp, qs, intra, bd)
+                assert nnz[b] == e_nnz and np.array_equal(coef[b], c), ("levels", lw, lh, qp, intra, b)
+                O.xo_dquant(ptr(c), lw, lh, dqs, bd)
+                O.xo_itrans(ptr(c), lw, lh, bd)
+                e = np.zeros((h, s), np.int16)
+                O.xo_recon(ptr(c), ptr(pred, b * n), 1, w, h, s, ptr(e), bd)
+                y0, x0 = offs[b] // s, offs[b] % s
+                assert np.array_equal(rec[y0:y0 + h, x0:x0 + w], e[:, :w]), ("rec", lw, lh, qp, intra, b)
+                assert ssd[b, 1] == O.xo_ssd(w, h, ptr(org, offs[b]), ptr(rec, offs[b]), s, s, bd)
+            if rdoq:
+                assert (wrapped_outputs(fwd, levels, coef) > 0) == wraps_expected(lw, lh, qp, bd), (lw, lh, qp, intra)
+            else:
+                assert (_plain_wrap_count(fwd, coef, lw, lh, qp, intra) > 0) == plain_wraps_expected(lw, lh, qp, bd), (lw, lh, qp, intra)

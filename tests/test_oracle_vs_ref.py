@@ -231,3 +231,32 @@ def test_recon():
             R.recon(ptr(coef), ptr(pred), is_coef, w, w, s_rec, ptr(r0), 10)
             O.xo_recon(ptr(coef), ptr(pred), is_coef, w, w, s_rec, ptr(r1), 10)
             assert np.array_equal(r0, r1)
+
+
+@pytest.mark.parametrize("lw,lh", [(2, 2), (3, 3), (4, 4), (5, 5), (6, 6), (4, 5), (6, 5)])
+def test_plain_quantisation_matches_reference_where_16_bit_levels_wrap(lw, lh):
+    """xo_trans + xo_quant against the reference's own transform and plain quantiser (xeve_sub_block_tq without RDOQ, oracle/ref_rdoq_driver.c refdrv_tq) on full-scale
+    residuals (_rdoq_cases.saturated_residuals) at QP 0 .. 9, I and B slices: the reference stores the level through an (s16) cast (xeve_tq.c:723-724), so above 32767 it
+    wraps -- 32-point blocks at QP 0 .. 3, 64-point blocks at QP 0 .. 9 at 10 bits -- and the test asserts that it did wherever a full-scale residual gets there"""
+    from _libs import ref_rdoq
+    from _rdoq_cases import QUANT_SCALE as scale, plain_levels, plain_wraps_expected, saturated_residuals
+
+    RQ = ref_rdoq()
+    if RQ is None or not hasattr(RQ, "refdrv_tq"):
+        pytest.skip("oracle/_ref/libref_rdoq.so not built (needs /root/reference)")
+    O = oracle()
+    for qp in range(10):
+        resid = saturated_residuals(lw, lh, qp, 10)
+        wrapped = 0
+        for slice_type, intra in ((2, 1), (0, 0)):  # XEVE_ST_I, XEVE_ST_B
+            for k in range(len(resid)):
+                a, b = resid[k].copy(), resid[k].copy()
+                n_ref = RQ.refdrv_tq(ptr(a), lw, lh, qp, slice_type, 10)
+                O.xo_trans(ptr(b), lw, lh, 10)
+                lev = plain_levels(b, lw, lh, qp, 10, intra)
+                n_or = O.xo_quant(ptr(b), lw, lh, qp, scale[qp % 6], intra, 10)
+                assert n_ref == n_or and np.array_equal(a, b), (lw, lh, qp, slice_type, k)
+                big = lev > 32767
+                wrapped += int((big & (np.abs(b.astype(np.int64)) == np.abs(lev.astype(np.int16).astype(np.int64)))).sum())  # the output IS the wrapped level
+                assert np.all(np.abs(b[big].astype(np.int64)) == np.abs(lev[big].astype(np.int16).astype(np.int64)))
+        assert (wrapped > 0) == plain_wraps_expected(lw, lh, qp, 10), (lw, lh, qp)

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from _libs import RdoqEst, oracle_rdoq, ptr
-from _rdoq_cases import make_coef, make_est
+from _rdoq_cases import SATURATED_GOLDEN_QPS, SATURATED_SIZES, make_coef, make_est, saturated_case, wrapped_outputs, wraps_expected
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rdoq_v1.npz")
 
@@ -73,6 +73,75 @@ def test_hip_rdoq_batches_vs_oracle(lw, lh):
             e = blocks[b].copy()
             en = O.xo_rdoq(ptr(e), lw, lh, qp, lam, luma, bd, 0, C.byref(est))
             assert nnz[b] == en and np.array_equal(got[b], e), (lw, lh, rep, b, qp, bd)
+
+
+GOLD_SATURATED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rdoq_saturated_v1.npz")
+_saturated_memo = {}
+
+
+def saturated_golden(lw, lh, qp, bd):
+    """a wrap-zone case (_rdoq_cases.saturated_case) with the REFERENCE's output levels and counts (tests/golden/rdoq_saturated_v1.npz, make_rdoq_golden.py saturated);
+    built once and shared, never written to"""
+    key = "%d_%d_%d_%d" % (lw, lh, qp, bd)
+    if key not in _saturated_memo:
+        if "npz" not in _saturated_memo:
+            _saturated_memo["npz"] = np.load(GOLD_SATURATED)
+        g = _saturated_memo["npz"]
+        blocks, est, lam, luma, levels = saturated_case(lw, lh, qp, bd)
+        assert np.array_equal(blocks, g["in_" + key]), key  # (the builder still makes the blocks the golden was recorded from)
+        for a in (blocks, levels):
+            a.setflags(write=False)
+        _saturated_memo[key] = (blocks, est, lam, luma, levels, g["out_" + key], g["nnz_" + key])
+    return _saturated_memo[key]
+
+
+@pytest.mark.parametrize("lw,lh", SATURATED_SIZES)
+def test_oracle_rdoq_matches_reference_goldens_where_16_bit_levels_wrap(lw, lh):
+    """the reference keeps quantised levels in (s16) without a clip (xeve_tq.c:558, 608): at 10 bits a full-scale coefficient passes 32767 on 32-point blocks at QP 0 .. 3
+    and on 64-point blocks at QP 0 .. 9, wraps, and the wrapped sign and magnitude go through the search, the rate and the output.  The oracle on the recorded cases
+    (QP 1, 3, 4, 9; 8 and 10 bits); wherever a 16-bit coefficient can reach such a level the cases do, and the wrap shows in the reference's outputs."""
+    O = oracle_rdoq()
+    seen = 0
+    for bd in (8, 10):
+        for qp in SATURATED_GOLDEN_QPS:
+            blocks, est, lam, luma, levels, gout, gnnz = saturated_golden(lw, lh, qp, bd)
+            assert (levels.max() > 32767) == wraps_expected(lw, lh, qp, bd)
+            for k in range(len(blocks)):
+                c = blocks[k].copy()
+                assert O.xo_rdoq(ptr(c), lw, lh, qp, lam, luma, bd, 0, C.byref(est)) == gnnz[k] and np.array_equal(c, gout[k]), (lw, lh, qp, bd, k)
+            if wraps_expected(lw, lh, qp, bd):
+                assert wrapped_outputs(blocks, levels, gout) > 0, (lw, lh, qp, bd)
+                seen += 1
+    assert seen == sum(wraps_expected(lw, lh, qp, 10) for qp in SATURATED_GOLDEN_QPS)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lw,lh", SATURATED_SIZES)
+def test_hip_rdoq_where_16_bit_levels_wrap(lw, lh):
+    """D.rdoq (rdoq.hip) on the same cases, nine blocks per size, QP and bit depth: levels and counts = the reference's (golden) = the oracle's.  At the sizes and QPs where
+    a level can pass 32767 the test asserts that some did and that the outputs show the wrap -- otherwise it would prove nothing."""
+    import torch
+
+    import xeve_amd
+    from xeve_amd import device as D
+    from xeve_amd import lib
+
+    xeve_amd.init(0)
+    dev = torch.device("cuda:0")
+    O = oracle_rdoq()
+    for bd in (8, 10):
+        for qp in SATURATED_GOLDEN_QPS:
+            blocks, est, lam, luma, levels, gout, gnnz = saturated_golden(lw, lh, qp, bd)
+            d = torch.from_numpy(blocks.copy()).to(dev)
+            nnz = D.rdoq(d, lw, lh, qp, lam, luma, bd, lib.RdoqEst.from_buffer_copy(bytes(est))).cpu().numpy()
+            got = d.cpu().numpy()
+            for k in range(len(blocks)):
+                e = blocks[k].copy()
+                en = O.xo_rdoq(ptr(e), lw, lh, qp, lam, luma, bd, 0, C.byref(est))
+                assert en == gnnz[k] and np.array_equal(e, gout[k]), ("oracle vs golden", lw, lh, qp, bd, k)
+                assert nnz[k] == gnnz[k] and np.array_equal(got[k], gout[k]), ("device vs golden", lw, lh, qp, bd, k)
+            if wraps_expected(lw, lh, qp, bd):
+                assert (levels > 32767).any() and wrapped_outputs(blocks, levels, got) > 0, (lw, lh, qp, bd)
 
 
 @pytest.mark.gpu
@@ -209,3 +278,47 @@ def test_hip_rdoq_with_device_estimates_vs_oracle(lw, lh):
             for b in range(0, len(blocks), 5):
                 e = blocks[b].copy()
                 assert nnz2[b] == O.xo_rdoq(ptr(e), lw, lh, qp, lam, int(ch_type == 0), bd, 0, C.byref(est)) and np.array_equal(d2[b].cpu().numpy(), e)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lw,lh", [(4, 4), (5, 5), (6, 6), (4, 5), (6, 5)])
+def test_hip_rdoq_with_device_estimates_where_16_bit_levels_wrap(lw, lh):
+    """D.rdoq_dev with the zero pre-test on the wrap-zone blocks at QP 1, 3, 4, 9 (10 bits): estimates from coder states on the device, their continue-bin entries capped
+    so that the reference's s32 rate holds (_rdoq_cases.rate_bound) -- levels and counts = the oracle's (pinned to the reference on these blocks by the golden tests
+    above); where a level can pass 32767 the outputs must show the wrapped value"""
+    import torch
+
+    import xeve_amd
+    from _libs import EST_FULL_INTS, oracle_sbac
+    from _rdoq_cases import rate_bound
+    from _sbac_cases import make_states
+    from xeve_amd import device as D
+
+    xeve_amd.init(0)
+    dev = torch.device("cuda:0")
+    O, OS = oracle_rdoq(), oracle_sbac()
+    states = make_states(np.random.default_rng(3400 + lw * 8 + lh), 5)
+    full = D.rdoq_bit_est(torch.from_numpy(states.view(np.uint8).copy()).to(dev)).cpu().numpy().reshape(len(states), EST_FULL_INTS).copy()
+    for qp in SATURATED_GOLDEN_QPS:
+        blocks, _, lam, _, levels, _, _ = saturated_golden(lw, lh, qp, 10)
+        capped = full.copy()
+        capped[:, 57:104:2] = np.minimum(capped[:, 57:104:2], rate_bound(levels))  # level[24][2] starts at int 56: the [.][1] entries
+        est_dev = torch.from_numpy(capped).to(dev)
+        idx = (np.arange(len(blocks)) % len(states)).astype(np.int32)
+        qs = D.QUANT_SCALE[0][qp % 6]
+        for ch_type, is_intra, slice_i in ((0, 0, 0), (0, 1, 1), (1, 0, 0)):
+            d = torch.from_numpy(blocks.copy()).to(dev)
+            nnz = D.rdoq_dev(d, lw, lh, qp, lam, ch_type, 10, est_dev, torch.from_numpy(idx).to(dev), zero_test=True, is_intra_slice=bool(slice_i), is_intra_cu=bool(is_intra)).cpu().numpy()
+            got = d.cpu().numpy()
+            for b in range(len(blocks)):
+                est = RdoqEst()
+                OS.xo_rdoq_est_select(ptr(capped[idx[b]:idx[b] + 1]), ch_type, is_intra, C.byref(est))
+                assert max(est.level[i][1] for i in range(24)) <= rate_bound(levels)
+                e = blocks[b].copy()
+                if O.xo_rdoq_zero_test(ptr(e), lw, lh, qp, qs, slice_i, 10):
+                    en = O.xo_rdoq(ptr(e), lw, lh, qp, lam, int(ch_type == 0), 10, 0, C.byref(est))
+                else:
+                    e[:], en = 0, 0
+                assert nnz[b] == en and np.array_equal(got[b], e), (lw, lh, qp, ch_type, is_intra, b)
+            if wraps_expected(lw, lh, qp, 10):
+                assert wrapped_outputs(blocks, levels, got) > 0, (lw, lh, qp, ch_type)

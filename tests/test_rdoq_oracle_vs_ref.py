@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from _libs import oracle_rdoq, ptr, ref_rdoq
-from _rdoq_cases import make_coef, make_est
+from _rdoq_cases import SATURATED_SIZES, make_coef, make_est, saturated_case, wrapped_outputs, wraps_expected
 
 pytestmark = pytest.mark.skipif(ref_rdoq() is None, reason="oracle/_ref/libref_rdoq.so not built (needs /root/reference)")
 
@@ -44,3 +44,23 @@ def test_rdoq_matches_reference(lw, lh):
         assert n_ref == n_or and np.array_equal(a, b), (lw, lh, it, qp, bd)
         nz_total += n_or
     assert nz_total > 0
+
+
+@pytest.mark.parametrize("lw,lh", SATURATED_SIZES)
+def test_rdoq_matches_reference_where_16_bit_levels_wrap(lw, lh):
+    """full-scale flat, step, checkerboard and stripe residuals and DC levels on 32767 / 32768 / beyond 65535 at QP 0 .. 9, 8 and 10 bits (_rdoq_cases.saturated_case): the
+    reference keeps levels in (s16) without a clip, so a level above 32767 wraps, and the wrapped value is what its search, its rate and its output work with -- the
+    oracle must make the same wrapped decisions.  Wherever a 16-bit coefficient can reach such a level the cases do, and that is asserted."""
+    O, R = oracle_rdoq(), ref_rdoq()
+    wrapped = 0
+    for bd in (8, 10):
+        for qp in range(10):
+            blocks, est, lam, luma, levels = saturated_case(lw, lh, qp, bd)
+            assert (levels.max() > 32767) == wraps_expected(lw, lh, qp, bd) and levels[6].max() >= min(32767, levels.max())
+            for k in range(len(blocks)):
+                a, b = blocks[k].copy(), blocks[k].copy()
+                n_ref = R.refdrv_rdoq(ptr(a), lw, lh, qp, lam, k & 1, 0 if luma else 1, bd, 0, C.byref(est))
+                n_or = O.xo_rdoq(ptr(b), lw, lh, qp, lam, luma, bd, 0, C.byref(est))
+                assert n_ref == n_or and np.array_equal(a, b), (lw, lh, qp, bd, k)
+                wrapped += wrapped_outputs(blocks[k], levels[k], b)
+    assert (wrapped > 0) == any(wraps_expected(lw, lh, qp, 10) for qp in range(10))

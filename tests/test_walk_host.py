@@ -251,3 +251,13 @@ def test_walk_decides_every_ctu_of_a_preset_slow_batch(walk_engine, tmp_path_fac
     data, fb = _clip(str(tmp_path_factory.getbasetemp()), name, w, h, gops * frames, seed), w * h * 3 // 2 * frames
     outs = _enc.encode_cpu(_enc.config(w, h, cli, threads), [data[i * fb:(i + 1) * fb] for i in range(gops)], frames)
     assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in g["per_gop"]]
+
+
+@pytest.mark.parametrize("name", sorted(_enc.SATURATED_CASES))
+def test_walk_decides_every_ctu_of_saturated_content(name, walk_engine, tmp_path_factory):
+    """0 / 255 content down to QP 0 (tests/_enc.py SATURATED_CASES) through the fused walk's host side: its own quantiser and RDOQ (cu_lane.h, walk.h) and the packed
+    run / level entries with their 15 level bits, where the reference's 16-bit levels wrap -- against the reference application's bitstreams"""
+    w, h, gops, frames, seed, cli, threads = _enc.SATURATED_CASES[name]
+    g = _enc.golden()["batches"][name]
+    outs = _enc.encode_cpu(_enc.config(w, h, cli, threads), _enc.qp_range_input(str(tmp_path_factory.getbasetemp()), name, _enc.SATURATED_CASES), frames)
+    assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in g["per_gop"]]

@@ -207,7 +207,7 @@ struct xeve_hip_enc {
     // ---- the engine (enc_host.h) --------------------------------------------------------------------------------------------------------------------------------
     Param P;
     int   G = 0, F = 0, T = 1, nslots = 0, w_scu = 0, h_scu = 0, w_lcu = 0, h_lcu = 0, f_lcu = 0, vh = 0, s_l = 0, s_c = 0;
-    long  org_l = 0, org_c = 0, pic_l = 0, pic_c = 0, map_pic = 0, frame_bytes = 0, slice_cap = 0;
+    long  org_l = 0, org_c = 0, pic_l = 0, pic_c = 0, map_pic = 0, frame_bytes = 0, slice_cap = 0, slice_told = 0;
     hipStream_t st = nullptr, st2 = nullptr, collect_stream = nullptr; // st2: the second writer pass, beside the next picture's steps
     hipEvent_t  ev_ready = nullptr, ev_done = nullptr;
     bool rows_pending = false, two_stores = false;
@@ -291,7 +291,14 @@ struct xeve_hip_enc {
         nslots = BatchEncoder<xeve_hip_enc>::slots_needed(P, F);
         if(nslots < 1) return fail("the frame loop needs more picture stores than there are");
         const std::vector<PicPlan> plan = Planner(P, F).run();
-        slice_cap = slice_capacity(P.w, P.h, lowest_slice_qp(P, plan)); // (sized by the run's lowest slice QP: enc_plan.h)
+        slice_cap = slice_told = slice_capacity(P.w, P.h, lowest_slice_qp(P, plan)); // (sized by the run's lowest slice QP: enc_plan.h)
+        // developer switch, read at create (tests/test_enc_gpu.py: the overflow path, reached without content that outgrows the rule): the bytes per GOP the writer
+        // kernels and fetch() are TOLD the buffer holds.  The allocation stays slice_cap; a value above it is refused.
+        if(const char *told = getenv("XEVE_HIP_ENC_SLICE_TOLD")) {
+            const long v = atol(told);
+            if(v < 1 || v > slice_cap) return fail("XEVE_HIP_ENC_SLICE_TOLD must lie in 1 .. the slice buffer's size");
+            slice_told = v;
+        }
         pos_of_frame.assign(F, -1);
         for(size_t i = 0; i < plan.size(); i++)
             if(plan[i].frame >= 0 && plan[i].frame < F && pos_of_frame[plan[i].frame] < 0) pos_of_frame[plan[i].frame] = (int)i;
@@ -483,7 +490,7 @@ struct xeve_hip_enc {
             return;
         if(keeps_store()) k_enc_keep<<<dim3(4, nch), 256, 0, st>>>(out.as<xeve_hip_ctu_data>(), store_now(), D, G, f_lcu);
         k_enc_write<<<nch, 64, 0, st>>>(out.as<xeve_hip_ctu_data>(), states.as<xeve_hip_sbac>(), E, scu.as<uint32_t>(), ipm.as<int8_t>(), tidx.as<uint8_t>(), cum.as<uint32_t>(), map_pic,
-                                        jobs.as<xeve_hip_ctu_job>(), nch, slice.as<uint8_t>(), rewrite_mode ? 0 : slice_cap, pos.as<int32_t>());
+                                        jobs.as<xeve_hip_ctu_job>(), nch, slice.as<uint8_t>(), rewrite_mode ? 0 : slice_told, pos.as<int32_t>());
         hip_ok(hipGetLastError(), "step kernels");
         n_steps++, t_steps += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
@@ -527,11 +534,11 @@ struct xeve_hip_enc {
             xl::EcoParams Ew = E; // (the pass's own copy: E follows the next picture)
             for(int row = 0; row < h_lcu; row++)
                 k_enc_rewrite<<<G, 64, 0, st2>>>(store_now(), fin, Ew, rw_scu.as<uint32_t>(), rw_ipm.as<int8_t>(), tidx.as<uint8_t>(), rw_cum.as<uint32_t>(), map_pic, G, f_lcu, w_lcu,
-                                                 row * w_lcu, (row + 1) * w_lcu, slice.as<uint8_t>(), slice_cap, pos.as<int32_t>());
+                                                 row * w_lcu, (row + 1) * w_lcu, slice.as<uint8_t>(), slice_told, pos.as<int32_t>());
             rows_pending = true;
             if(two_stores) cur_store ^= 1;
         }
-        k_enc_tile_end<<<G, 64, 0, ws_>>>(fin, fin_stride, G, slice.as<uint8_t>(), slice_cap, pos.as<int32_t>());
+        k_enc_tile_end<<<G, 64, 0, ws_>>>(fin, fin_stride, G, slice.as<uint8_t>(), slice_told, pos.as<int32_t>());
         for(int g = 0; g < G; g++) // xeve_pic_finish: the picture becomes a reference
             if(!rc_ok(xeve_hip_picbuf_expand(slot_plane(S.cur_slot, 0) + (size_t)g * pic_l, slot_plane(S.cur_slot, 1) + (size_t)g * pic_c, slot_plane(S.cur_slot, 2) + (size_t)g * pic_c,
                                              s_l, s_c, P.w, P.h, P.w / 2, P.h / 2, PAD_L, PAD_C, 1, st),
@@ -564,9 +571,9 @@ struct xeve_hip_enc {
         if(!hip_ok(hipEventSynchronize(ev_done), "hipEventSynchronize")) return;
         slice_data.resize(G), bins.resize(G);
         for(int g = 0; g < G; g++) {
-            if(h_pos[g] < 0 || h_pos[g] > slice_cap) { fail("a picture's slice data outgrew its buffer"); slice_data.clear(), bins.clear(); return; }
+            if(h_pos[g] < 0 || h_pos[g] > slice_told) { fail("a picture's slice data outgrew its buffer"); slice_data.clear(), bins.clear(); return; }
             slice_data[g].resize(h_pos[g]);
-            if(h_pos[g] && !hip_ok(hipMemcpyAsync(slice_data[g].data(), slice.as<uint8_t>() + (size_t)g * slice_cap, h_pos[g], hipMemcpyDeviceToHost, collect_stream), "copy slice data")) {
+            if(h_pos[g] && !hip_ok(hipMemcpyAsync(slice_data[g].data(), slice.as<uint8_t>() + (size_t)g * slice_told, h_pos[g], hipMemcpyDeviceToHost, collect_stream), "copy slice data")) {
                 slice_data.clear(), bins.clear();
                 return;
             }

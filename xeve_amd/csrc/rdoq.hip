@@ -59,13 +59,17 @@ __device__ __forceinline__ Cand eval_coef(int v, const RdoqK &P, const Est12 &E)
     unsigned m = (unsigned)(ld >> P.q_bits);
     if(!((ld - ((long)m << P.q_bits)) < (1L << (P.q_bits - 1)))) m++;
     const long e1 = (ld * P.err_scale) >> 20;
-    c.unc = e1 * e1, c.maxabs = m, c.neg = !(v > 0);
-    const unsigned lo = m > 1 ? m - 1 : 1;
+    // the reference keeps the level in an s16 (tmp_coef, xeve_tq.c:558: a plain cast, no clip): above 32767 it wraps, and the wrapped value's magnitude and sign are
+    // what the search below and the output work with (32-point blocks at QP 0 .. 3, 64-point blocks at QP 0 .. 9; sum_all keeps the unwrapped level)
+    const int w16 = (int16_t)(v > 0 ? (int)(int16_t)m : -(int)(int16_t)m);
+    const unsigned ma = (unsigned)(w16 < 0 ? -w16 : w16);
+    c.unc = e1 * e1, c.maxabs = m, c.neg = w16 < 0;
+    const unsigned lo = ma > 1 ? ma - 1 : 1;
 #pragma unroll
     for(int rs = 0; rs < 2; rs++) {
         long coded = c.unc + rl_cost(0, rs, P, E);
         unsigned best = 0;
-        for(unsigned a = m; a >= lo; a--) {
+        for(unsigned a = ma; a >= lo; a--) {
             const long dd = ld - ((long)a << P.q_bits), e2 = (dd * P.err_scale) >> 20, cost = e2 * e2 + rl_cost(a, rs, P, E);
             if(cost < coded) best = a, coded = cost;
         }

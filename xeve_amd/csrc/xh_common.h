@@ -16,6 +16,8 @@ typedef int16_t pel;
 //   XEVE_HIP_ENC_TWO_STORES = 0                                    one CTU store instead of two
 //   XEVE_HIP_ENC_PRIO = 1, XEVE_HIP_ENC_FULL_STATES = 1            the encoder's main stream above its second-pass stream; complete coder states through the walk
 //   XEVE_HIP_ENC_SHARE = 0                                         every picture store in memory of its own (default: later stores over the frames already coded, encode.hip)
+//   XEVE_HIP_ENC_SLICE_TOLD = n                                    (the one switch results DO depend on; read at every create) the writers and the fetch are told a slice
+//                                                                  buffer of n bytes per GOP, at most the allocated size: the overflow error, reached by a test
 //   XEVE_HIP_HOST_GRAPH = 0                                        the host-memory form of the inter analysis without its per-CU graph replay
 //   XEVE_HIP_WALK_C / _NT / _SPREAD / _DEAL / _INTER / _COUNT / _PROF / _DBG   the fused kernel's team shape, wave placement, stage profile and debug counters (walk.hip)
 // ---- error plumbing (abi.cpp) -------------------------------------------------------------
