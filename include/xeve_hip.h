@@ -905,7 +905,8 @@ typedef struct xeve_hip_enc_config {
     int32_t inter_slice_type; /* --inter-slice-type: 0 B, 1 P */
     int32_t ref;              /* --ref (0: the preset's) */
     int32_t reserved[4];      /* [0] bit 0: always run the second writer pass (tests); bit 1: the application's --info 0 (no SEI with the option list); bit 2: measure every picture (xeve_hip_enc_picture_info's
-                               * sse / psnr); bit 3: keep the reconstructed pictures (xeve_hip_enc_recon; w * h * 3 bytes per picture of the batch); bits 8-15: --level-idc (0: 40).  [1]: the application's -d, the input's bit depth -- 0 / 8: one byte per sample;
+                               * sse / psnr); bit 3: keep the reconstructed pictures (xeve_hip_enc_recon; w * h * 3 bytes per picture of the batch); bit 4: the application's --hash -- every picture is followed by a
+                               * picture-signature SEI with the MD5 of each decoded plane, hashed on the device (xeve_hip_enc_signature; 48 bytes per picture of the batch); bits 8-15: --level-idc (0: 40).  [1]: the application's -d, the input's bit depth -- 0 / 8: one byte per sample;
                                * 10: 16-bit little-endian samples (frames pushed are twice as long).  Either way the codec works at 10 bits (--codec-bit-depth).  [2], [3]: --qp-cb-offset / --qp-cr-offset, -12 .. 12
                                * (pinned against the reference LIBRARY: the application lists the options and cannot parse them; 0 with presets slow / placebo). */
 } xeve_hip_enc_config;
@@ -971,6 +972,31 @@ int xeve_hip_enc_recon(xeve_hip_enc *e, int gop, int frame, void *dst, int on_de
  * written.  Two launches (luma, chroma) whatever npics is; npics at most 65535.  Everything is device memory. */
 int xeve_hip_recon_measure(const uint16_t *const rec[3], int s_rec_l, int s_rec_c, int64_t rec_pic_l, int64_t rec_pic_c, const uint16_t *const org[3], int s_org_l, int s_org_c,
                            int64_t org_pic_l, int64_t org_pic_c, int w, int h, int npics, uint16_t *out, int64_t out_pic, uint64_t *sse, void *stream);
+
+/* The application's --hash (reserved[0] bit 4): behind every picture's slice NAL unit the bitstream carries a picture-signature SEI NAL unit at the picture's temporal id
+ * (xeve_pic_finish, src_base/xeve_enc.c:1255-1271; xeve_eco_signature, xeve_eco.c:300-322) -- payload type 0x10, the size byte 0x10, then the MD5 of the decoded Y, U and V
+ * plane (the size byte says 16 although 48 bytes follow: reproduced as it is).  The unit is always XEVE_HIP_SIGNATURE_SEI_BYTES long, and the SEI with the option list in
+ * front of an IDR picture says hash=1.  Each MD5 is the standard one over the plane's interior as the -r file holds it: rows of w (w / 2) 16-bit little-endian samples
+ * at the codec's 10 bits, no padding (xeve_md5_imgb, xeve_util.c:1067-1083).  A decoder checks its own pictures against these.  The digests are made on the device at the
+ * picture's end, behind the loop filter; without bit 4 nothing is allocated or launched.
+ * xeve_hip_enc_picture.bytes stays the application's Bits / 8, which does NOT count the signature unit: with bit 4 the access unit in the bitstream is
+ * bytes + XEVE_HIP_SIGNATURE_SEI_BYTES long. */
+#define XEVE_HIP_SIGNATURE_SEI_BYTES 56
+/* The three digests (Y, U, V; 16 bytes each) of a picture whose access unit is in the bitstream: the validity rules of xeve_hip_enc_picture_info; needs bit 4. */
+int xeve_hip_enc_signature(xeve_hip_enc *e, int gop, int frame, uint8_t out[48]);
+/* The signature unit itself from a temporal id (0 .. 7) and three digests: host only, no device call, usable before xeve_hip_init.  Writes and returns
+ * XEVE_HIP_SIGNATURE_SEI_BYTES; a negative error code when out is NULL, cap too small or tid out of range. */
+int xeve_hip_signature_sei(int tid, const uint8_t digests[48], uint8_t *out, size_t cap);
+/* The kernel behind the digests, as a leaf: job j's message is h rows of w 16-bit samples read from base + offset as they lie in memory (little-endian), rows `stride`
+ * samples apart, joined without padding; digests[j] = its MD5.  w, h >= 1, stride >= w; any 2-byte alignment (rows on 16-byte boundaries that are a whole number of
+ * 64-byte blocks long are read fastest).  One launch whatever njobs is, a lane per job, no workspace: list jobs of one length next to each other -- a wave of 64 lanes
+ * is as slow as its longest message.  base, jobs and digests are device memory; only the described samples are read, only digests[0 .. njobs * 16) is written. */
+typedef struct xeve_hip_md5_job {
+    int64_t offset;        /* samples from base to the first sample */
+    int32_t stride, w, h;  /* samples */
+    int32_t reserved;
+} xeve_hip_md5_job;
+int xeve_hip_md5_planes(const uint16_t *base, const xeve_hip_md5_job *jobs, int njobs, uint8_t *digests /* [njobs][16] */, void *stream);
 
 /* ------------------------------------------------------------------------------------------- */
 /* Main profile: the adaptive loop filter's sample kernels ("ALF           */

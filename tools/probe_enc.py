@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Times the batch encoder in chunks of lockstep steps (device fence after every chunk): where a picture's time goes -- the steps of the I picture, of the inter
-picture, the picture ends.  usage: probe_enc.py --width W --height H --gops G --threads T --frames F --chunk N [--content noise|moving] [--preset P]"""
+picture, the picture ends.  usage: probe_enc.py --width W --height H --gops G --threads T --frames F --chunk N [--content noise|moving] [--preset P] [--hash]
+--hash: the run makes the decoded-picture signatures (config(hash=True)); a picture's LAST step becomes a chunk of its own, so that chunk's wall time is one step plus
+the picture's end (loop filter, the 3 * G MD5s, the second writer pass, padding -- the fence waits for both streams), and after the run the MD5 leaf alone is timed on a
+store of the run's geometry: what one picture end adds, and the kernel's ns per 64-byte block of its longest (luma) message."""
 import argparse
 import hashlib
 import json
@@ -24,6 +27,8 @@ def main():
     ap.add_argument("--preset", default="medium", help="fast | medium | slow | placebo (slow and placebo run on the fused walk at any width)")
     ap.add_argument("--same-clip", action="store_true", help="every GOP codes the SAME frames: all bitstreams must come out equal -- a lockstep chain that goes wrong anywhere in the batch shows as a second md5")
     ap.add_argument("--prof-after", type=int, default=-1, help="switch the walk's in-kernel stage profile on once this many steps are done (e.g. a picture's steps: the inter picture alone)")
+    ap.add_argument("--hash", action="store_true", help="code with the picture signatures and time what a picture end adds (see above)")
+    ap.add_argument("--split-end", action="store_true", help="a picture's last step as a chunk of its own, as --hash does (the same run without the signatures, to compare)")
     a = ap.parse_args()
     import torch
 
@@ -34,7 +39,7 @@ def main():
     dev = torch.device("cuda", 0)
     W, H, F, G = a.width, a.height, a.frames, a.gops
     fb = W * H * 3 // 2
-    cfg = encode.config(W, H, qp=32, keyint=8, bframes=15, closed_gop=True, preset=a.preset, threads=a.threads)
+    cfg = encode.config(W, H, qp=32, keyint=8, bframes=15, closed_gop=True, preset=a.preset, threads=a.threads, hash=a.hash)
     t0 = time.perf_counter()
     enc = encode.BatchEncoder(cfg, G, F)
     gen = torch.Generator(device=dev)
@@ -64,6 +69,8 @@ def main():
     done, left = 0, total
     while left > 0 and (a.max_steps == 0 or done < a.max_steps):
         n = min(a.chunk, per_pic - done % per_pic)  # (a chunk never crosses a picture's end: its last step carries the picture end)
+        if (a.hash or a.split_end) and n > 1 and done % per_pic + n == per_pic:
+            n -= 1
         if a.prof_after >= 0 and done >= a.prof_after and not os.environ.get("XEVE_HIP_WALK_PROF"):
             from xeve_amd import lib
             lib.load().xeve_hip_walk_prof_enable(1)
@@ -91,6 +98,44 @@ def main():
                       "md5_of_all": hashlib.md5(b"".join(enc.bitstreams())).hexdigest() if left == 0 else None,
                       "distinct_bitstreams": (lambda m: {"count": len(set(m)), "gops_that_differ_from_gop_0": [i for i, x in enumerate(m) if x != m[0]][:40]})([hashlib.md5(b).hexdigest() for b in enc.bitstreams()]) if left == 0 and a.same_clip else None}), flush=True)
     enc.close()
+    if a.hash:
+        print(json.dumps(time_md5_leaf(torch, dev, W, H, G)), flush=True)
+
+
+def time_md5_leaf(torch, dev, W, H, G, reps=3):
+    """xeve_hip_md5_planes over G stacked pictures laid out as the encoder's picture stores are (luma stride W + 288, chroma W / 2 + 144, pictures a multiple of 64 rows
+    apart), the 3 * G jobs in the encoder's order (every luma plane, then every U, then every V): milliseconds per launch, and per 64-byte block of a luma message"""
+    import ctypes as C
+
+    import numpy as np
+
+    from xeve_amd import lib
+
+    L = lib.load()
+    vh, s_l, s_c = (H + 288 + 63) & ~63, W + 288, W // 2 + 144
+    pic_l, pic_c = vh * s_l, (vh // 2) * s_c
+    store = torch.randint(0, 1024, (G * (pic_l + 2 * pic_c),), dtype=torch.int16, device=dev)
+    jobs = np.zeros(3 * G, dtype=lib.MD5_JOB_DTYPE)
+    for c in range(3):
+        for g in range(G):
+            off = 144 * s_l + 144 + g * pic_l if c == 0 else G * pic_l + (c - 1) * G * pic_c + 72 * s_c + 72 + g * pic_c
+            jobs[c * G + g] = (off, s_c if c else s_l, W // 2 if c else W, H // 2 if c else H, 0)
+    d_jobs = torch.from_numpy(jobs.view(np.uint8).copy()).to(dev)
+    out = torch.zeros(3 * G * 16, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps + 1):
+        t = time.perf_counter()
+        lib.check(L.xeve_hip_md5_planes(C.c_void_p(store.data_ptr()), C.c_void_p(d_jobs.data_ptr()), 3 * G, C.c_void_p(out.data_ptr()), None))
+        torch.cuda.synchronize()
+        ms.append(1e3 * (time.perf_counter() - t))
+    import hashlib
+
+    plane = store[144 * s_l + 144:144 * s_l + 144 + (H - 1) * s_l + W].cpu().numpy()
+    want = hashlib.md5(b"".join(plane[r * s_l:r * s_l + W].astype("<i2").tobytes() for r in range(H))).digest()
+    blocks = W * H * 2 // 64
+    return {"md5_leaf": {"jobs": 3 * G, "launch_ms": [round(x, 3) for x in ms[1:]], "first_launch_ms": round(ms[0], 3), "luma_blocks": blocks,
+                         "ns_per_block": round(1e6 * min(ms[1:]) / blocks, 1), "gop0_luma_equals_hashlib": bytes(out[:16].cpu().numpy()) == want}}
 
 
 if __name__ == "__main__":

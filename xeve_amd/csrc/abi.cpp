@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "xh_common.h"
+#include "enc_plan.h"
 
 int xh_tq_init();
 int xh_main_tools_init(); // main_tools.hip: the ATS matrices
@@ -731,4 +732,14 @@ extern "C" int xeve_hip_install_tables_main(void *fn_itxb_slot)
         n++;
     }
     return n;
+}
+
+// the picture-signature SEI NAL unit of --hash from a temporal id and three digests (enc_plan.h make_signature_sei): host only, no device call
+extern "C" int xeve_hip_signature_sei(int tid, const uint8_t digests[48], uint8_t *out, size_t cap)
+{
+    XH_REQUIRE(digests && out && tid >= 0 && tid <= 7 && cap >= XEVE_HIP_SIGNATURE_SEI_BYTES);
+    const std::vector<uint8_t> unit = xenc::make_signature_sei(tid, digests);
+    if(unit.size() != XEVE_HIP_SIGNATURE_SEI_BYTES) { xh_set_error("xeve_hip_signature_sei: internal error (a unit of %zu bytes)", unit.size()); return XEVE_HIP_ERR_ARG; }
+    memcpy(out, unit.data(), unit.size());
+    return XEVE_HIP_SIGNATURE_SEI_BYTES;
 }

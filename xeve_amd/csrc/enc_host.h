@@ -16,8 +16,14 @@
 //                                                 // ISSUES the work: the next picture may begin while the second writer pass is still running
 //       void collect(std::vector<std::vector<uint8_t>> &slice_data, std::vector<uint32_t> &bins);
 //                                                 // the slice data + bin count of the picture last ended (waits for it); called before the next end_picture
+//       bool picture_digests(std::vector<uint8_t> &d);
+//                                                 // OPTIONAL (--hash): d[g * 48 ..] = the MD5 of GOP g's decoded Y, U and V plane of that same picture, behind the loop
+//                                                 // filter (xeve_md5_imgb); called behind collect.  An engine without the member cannot code with Param::hash:
+//                                                 // begin() refuses the run
 //   };
 #pragma once
+#include <type_traits>
+#include <utility>
 #include "enc_plan.h"
 
 namespace xenc __attribute__((visibility("hidden"))) { // (hidden: the test harness instantiates the same inline code in its own library, and the two must not bind to each other)
@@ -31,6 +37,10 @@ struct PicSetup {
     xeve_hip_eco_params     ep;
     xeve_hip_deblock_params dp;
 };
+
+template <class Engine, class = void> struct engine_has_digests : std::false_type {};
+template <class Engine>
+struct engine_has_digests<Engine, std::void_t<decltype(std::declval<Engine &>().picture_digests(std::declval<std::vector<uint8_t> &>()))>> : std::true_type {};
 
 template <class Engine> class BatchEncoder {
   public:
@@ -59,6 +69,7 @@ template <class Engine> class BatchEncoder {
     {
         out = &out_;
         out->assign(G, std::vector<uint8_t>());
+        if(P.hash && !engine_has_digests<Engine>::value) return fail("--hash needs an engine that hashes the decoded pictures (picture_digests): this one does not");
         // low-delay closed GOPs with an odd keyint over more than one GOP: the reference keeps two input slots there (xeve_enc.c:1693-1695), files a frame under its count
         // in the SEQUENCE (:661) and fetches it under its count in the GOP (:1080) -- with an odd keyint the two part ways after the first GOP and it codes stale slots
         if(P.bframes == 0 && P.closed_gop && P.keyint > 1 && (P.keyint & 1) && F > P.keyint)
@@ -132,6 +143,7 @@ template <class Engine> class BatchEncoder {
     PicSetup S;
     std::vector<std::vector<uint8_t>> slice;
     std::vector<uint32_t> bins;
+    std::vector<uint8_t> digests; // [G][48] of the picture being finished (--hash)
     int fail(const char *m) { error = m; return -1; }
 
     // the set-up of picture pp against the bookkeeping d (xeve_pic_prepare, xeve_set_sh, xeve_picman_refp_init); nullptr: fine, else what is wrong
@@ -173,6 +185,11 @@ template <class Engine> class BatchEncoder {
         pending = -1;
         E.collect(slice, bins);
         if((int)slice.size() != G || (int)bins.size() != G) return fail("the engine returned no slice data");
+        if(P.hash) {
+            bool got = false;
+            if constexpr(engine_has_digests<Engine>::value) got = E.picture_digests(digests);
+            if(!got || digests.size() != (size_t)G * 48) return fail("the engine returned no picture digests");
+        }
         // the access unit: parameter sets in front of an IDR picture (xeve_header), then the slice NAL unit (xeve_pic :466-590)
         for(int g = 0; g < G; g++) {
             std::vector<uint8_t> &o = (*out)[g];
@@ -196,6 +213,10 @@ template <class Engine> class BatchEncoder {
             }
             nal_close(nal);
             o.insert(o.end(), nal.begin(), nal.end());
+            if(P.hash) { // xeve_pic_finish (:1255-1271): the signature unit behind the slice, at the picture's temporal id
+                const std::vector<uint8_t> sig = make_signature_sei(pp.tid, digests.data() + (size_t)g * 48);
+                o.insert(o.end(), sig.begin(), sig.end());
+            }
         }
         return 0;
     }

@@ -31,6 +31,7 @@ struct Param {
     int preset = 1; // 0 fast, 1 medium, 2 slow, 3 placebo
     int qp_cb_offset = 0, qp_cr_offset = 0; // --qp-cb-offset / --qp-cr-offset (sh->qp_u_offset / qp_v_offset, xeve_enc.c:1509-1510)
     int level_idc = 40, sei_info = 1; // --level-idc (sps->level_idc = 3 x, xeve_enc.c:1402) and --info (the SEI that lists the options, :1989)
+    int hash = 0; // --hash: a picture-signature SEI behind every picture (use_pic_sign, xeve_enc.c:1255-1271)
     int input_depth = 8; // the application's -d: 8 = one byte per sample, 10 = 16-bit little-endian samples (both go to the codec's 10 bits, xeve_app.c:1153-1158)
     // derived
     int gop_size = 16, ref_pic_gap_length = 0, me_ref_num = 1, me_range = 64, me_sub = 2, me_sub_pos = 4, me_sub_range = 1, merge_num = 3, me_algo = 1, rdo_dbk = 0;
@@ -42,7 +43,7 @@ struct Param {
         w = c.w, h = c.h, fps_num = c.fps_num, fps_den = c.fps_den, qp = c.qp, keyint = c.keyint, bframes = c.bframes, closed_gop = c.closed_gop != 0;
         threads = c.threads, inter_slice_type = c.inter_slice_type, ref = c.ref, preset = c.preset, input_depth = c.reserved[1] ? c.reserved[1] : 8;
         qp_cb_offset = c.reserved[2], qp_cr_offset = c.reserved[3];
-        level_idc = ((c.reserved[0] >> 8) & 0xFF) ? ((c.reserved[0] >> 8) & 0xFF) : 40, sei_info = (c.reserved[0] & 2) ? 0 : 1;
+        level_idc = ((c.reserved[0] >> 8) & 0xFF) ? ((c.reserved[0] >> 8) & 0xFF) : 40, sei_info = (c.reserved[0] & 2) ? 0 : 1, hash = (c.reserved[0] & 16) ? 1 : 0;
         auto bad = [&](const char *m) { error = m; return false; };
         if(w <= 0 || h <= 0 || (w & 7) || (h & 7)) return bad("picture size must be a positive multiple of 8 in both directions");
         if(w > 8192 || h > 4320) return bad("picture larger than 8192x4320");
@@ -418,7 +419,7 @@ inline std::string sei_text(const Param &P) // xeve_eco_emitsei's banner + xeve_
     std::string s = " xeve - MPEG-5 EVC codec - ESSENTIAL VIDEO CODING https://github.com/mpeg5/xeve - options: ";
     struct KV { const char *k; int v; };
     s += fmt("profile=%d threads=%d input-res=%dx%d fps=%.3f keyint=%d color-space=%d rc-type=CQP", 0, P.threads, P.w, P.h, (float)P.fps_num / P.fps_den, P.keyint, cs);
-    const KV a[] = {{"qp", P.qp}, {"qp_cb_offset", P.qp_cb_offset}, {"qp_cr_offset", P.qp_cr_offset}, {"info", P.sei_info}, {"hash", 0}, {"bframes", P.bframes}, {"aq-mode", 0}, {"lookahead", P.lookahead},
+    const KV a[] = {{"qp", P.qp}, {"qp_cb_offset", P.qp_cb_offset}, {"qp_cr_offset", P.qp_cr_offset}, {"info", P.sei_info}, {"hash", P.hash}, {"bframes", P.bframes}, {"aq-mode", 0}, {"lookahead", P.lookahead},
                     {"closed-gop", P.closed_gop}, {"disable-hgop", 0}, {"ref_pic_gap_length", P.ref_pic_gap_length}, {"codec-bit-depth", BIT_DEPTH}, {"level-idc", P.level_idc},
                     {"cu-tree", 0}, {"constrained-ip", 0}, {"use-deblock", 1}, {"inter-slice-type", P.inter_slice_type}, {"rdo-deblk-switch", P.rdo_dbk},
                     {"qp-increased-frame", 0}, {"forced-idr-frame-flag", 0}, {"qp-increased-frame", 0}};
@@ -448,6 +449,18 @@ inline std::vector<uint8_t> make_sei(const Param &P, int tid) // xeve_encode_sei
     for(uint8_t u : uuid) bs.put(u, 8);
     for(char c : t) bs.put((uint8_t)c, 8);
     bs.align();
+    nal_close(bs.b);
+    return bs.b;
+}
+// The picture-signature SEI of --hash (xeve_pic_finish, xeve_enc.c:1255-1271 -> xeve_eco_sei -> xeve_eco_signature, xeve_eco.c:300-322): payload type 0x10, the size
+// byte 0x10 and then ALL THREE planes' digests -- the size byte says 16 although 48 bytes follow, and nothing comes after them.  Always 56 bytes.
+enum { SIGNATURE_SEI_BYTES = 56 };
+inline std::vector<uint8_t> make_signature_sei(int tid, const uint8_t digests[48])
+{
+    Bits bs;
+    nal_open(bs, NUT_SEI, tid);
+    bs.put(0x10, 8), bs.put(16, 8); // XEVE_UD_PIC_SIGNATURE, payload_size
+    for(int i = 0; i < 48; i++) bs.put(digests[i], 8);
     nal_close(bs.b);
     return bs.b;
 }

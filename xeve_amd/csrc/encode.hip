@@ -177,6 +177,18 @@ __global__ void __launch_bounds__(64) k_enc_tile_end(xeve_hip_sbac *__restrict__
     xl::eco_tile_end(s, &o);
     states[(long)g * stride] = s, pos[g] = at + o.n;
 }
+// the picture end's 3 * G messages for xeve_hip_md5_planes: every luma plane, then every U, then every V plane (messages of one length side by side in a wave);
+// offsets from GOP 0's luma sample (0, 0)
+__global__ void k_enc_md5_jobs(xeve_hip_md5_job *__restrict__ jobs, int G, long off_u, long off_v, long pic_l, long pic_c, int s_l, int s_c, int w, int h)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if(j >= 3 * G) return;
+    const int c = j / G, g = j - c * G;
+    xeve_hip_md5_job J;
+    J.offset = c == 0 ? g * pic_l : (c == 1 ? off_u : off_v) + g * pic_c;
+    J.stride = c ? s_c : s_l, J.w = c ? w / 2 : w, J.h = c ? h / 2 : h, J.reserved = 0;
+    jobs[j] = J;
+}
 __global__ void k_enc_clear_cod(uint32_t *__restrict__ map_scu, long n)
 {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -250,12 +262,32 @@ struct xeve_hip_enc {
     std::vector<char>     sums_read;   // per coding position
     int n_served = 0;                  // pictures, in coding order, whose access unit is in the bitstream
     int device = -1;                   // the GPU the batch lives on (create)
+    // --hash (reserved[0] bit 4): the MD5 of every decoded plane, made at the picture's end on the main stream and copied out behind it on the same stream.  digs and the
+    // pinned h_digs hold a slot per picture of the run -- [display frame][plane][GOP][16] -- because finish_picture reads picture N's digests after picture N + 1's steps
+    // (and, at the run's end, its end) have been issued.  ev_digs: the copy of the picture last ended.
+    DevBuf      digs;
+    uint8_t    *h_digs = nullptr;
+    hipEvent_t  ev_digs = nullptr;
+    int         digs_frame = -1; // the display frame of the picture last ended
     bool measures() const { return (P_reserved0 & 4) != 0; }
     bool keeps_recon() const { return (P_reserved0 & 8) != 0; }
+    bool hashes() const { return (P_reserved0 & 16) != 0; }
+    // enc_host.h's optional member: the digests of the picture last ended, [GOP][Y, U, V]
+    bool picture_digests(std::vector<uint8_t> &d)
+    {
+        if(!hashes() || digs_frame < 0 || !error.empty() || !hip_ok(hipEventSynchronize(ev_digs), "hipEventSynchronize")) return false;
+        d.resize((size_t)G * 48);
+        for(int g = 0; g < G; g++) copy_digests(digs_frame, g, d.data() + (size_t)g * 48);
+        return true;
+    }
+    void copy_digests(int frame, int g, uint8_t out[48]) const
+    {
+        for(int c = 0; c < 3; c++) memcpy(out + 16 * c, h_digs + (((size_t)frame * 3 + c) * G + g) * 16, 16);
+    }
     size_t pic_samples() const { return (size_t)P.w * P.h * 3 / 2; }
     bool begin_run()
     {
-        n_served = 0;
+        n_served = 0, digs_frame = -1;
         au_at.assign((size_t)F * G, 0), h_sums.assign((size_t)F * G * 3, 0), sums_read.assign(F, 0);
         return !measures() || hip_ok(hipMemsetAsync(sums.p, 0, sums.bytes, st), "hipMemset");
     }
@@ -330,6 +362,7 @@ struct xeve_hip_enc {
         if(rewrite_mode) v.insert(v.end(), {{&store2[0], store_bytes()}, {&rw_scu, m * 4}, {&rw_cum, m * 4}, {&rw_ipm, m}});
         if(keeps_recon()) v.push_back({&kept, (size_t)G * F * pic_samples() * 2});
         if(measures()) v.push_back({&sums, (size_t)G * F * 3 * sizeof(uint64_t)});
+        if(hashes()) v.push_back({&digs, (size_t)G * F * 48});
         return v;
     }
     size_t store_bytes() const { return (size_t)G * f_lcu * sizeof(xl::CtuSyntax); }
@@ -386,6 +419,9 @@ struct xeve_hip_enc {
         if(!hip_ok(hipHostMalloc((void **)&h_states, (size_t)G * sizeof(xeve_hip_sbac), hipHostMallocDefault), "hipHostMalloc") ||
            !hip_ok(hipHostMalloc((void **)&h_pos, (size_t)G * 4, hipHostMallocDefault), "hipHostMalloc"))
             return false;
+        if(hashes() && (!hip_ok(hipHostMalloc((void **)&h_digs, (size_t)G * F * 48, hipHostMallocDefault), "hipHostMalloc") ||
+                        !hip_ok(hipEventCreateWithFlags(&ev_digs, hipEventDisableTiming), "hipEventCreate")))
+            return false;
         return hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize");
     }
     int P_reserved0 = 0; // bit 0: always run the second writer pass (tests)
@@ -404,6 +440,8 @@ struct xeve_hip_enc {
         if(ev_done) (void)hipEventDestroy(ev_done);
         if(h_states) (void)hipHostFree(h_states);
         if(h_pos) (void)hipHostFree(h_pos);
+        if(ev_digs) (void)hipEventDestroy(ev_digs);
+        if(h_digs) (void)hipHostFree(h_digs);
     }
 
     // the device side of an inter picture's set-up: the reference table and the motion maps of the stores the frame loop named
@@ -516,6 +554,18 @@ struct xeve_hip_enc {
                                              (int64_t)pic_samples(), measures() ? sums.as<uint64_t>() + at * 3 : nullptr, st),
                       "xeve_hip_recon_measure"))
                 return;
+        }
+        if(hashes()) { // the same place: the 3 * G planes of the store in ONE launch, and their 48 * G bytes to the host on the stream that made them
+            // (the job list lies in `out`: the step's CTU records are dead between the last step's writer and the next picture's first walk, both on this stream)
+            static_assert(sizeof(xeve_hip_ctu_data) >= 3 * sizeof(xeve_hip_md5_job), "a chain's CTU record holds a GOP's three jobs");
+            const pel *y = slot_plane(S.cur_slot, 0);
+            const size_t at = (size_t)S.frame * G * 48;
+            k_enc_md5_jobs<<<(3 * G + 255) / 256, 256, 0, st>>>(out.as<xeve_hip_md5_job>(), G, (long)(slot_plane(S.cur_slot, 1) - y), (long)(slot_plane(S.cur_slot, 2) - y), pic_l, pic_c,
+                                                                s_l, s_c, P.w, P.h);
+            if(!rc_ok(xeve_hip_md5_planes(reinterpret_cast<const uint16_t *>(y), out.as<xeve_hip_md5_job>(), 3 * G, digs.as<uint8_t>() + at, st), "xeve_hip_md5_planes") ||
+               !hip_ok(hipMemcpyAsync(h_digs + at, digs.as<uint8_t>() + at, (size_t)G * 48, hipMemcpyDeviceToHost, st), "copy digests") || !hip_ok(hipEventRecord(ev_digs, st), "event"))
+                return;
+            digs_frame = S.frame;
         }
         fin = states.as<xeve_hip_sbac>(), fin_stride = T;
         hipStream_t ws_ = st;
@@ -731,11 +781,22 @@ extern "C" int xeve_hip_enc_picture_info(xeve_hip_enc *e, int gop, int frame, xe
     memset(out, 0, sizeof(*out));
     out->frame = pp.frame, out->poc = pp.poc, out->slice_type = pp.slice_type, out->tid = pp.tid, out->qp = slice_qp(e->P, pp.depth), out->idr = pp.idr, out->coding_pos = k;
     out->bytes = (k + 1 < e->n_served ? e->au_at[(size_t)(k + 1) * e->G + gop] : e->bitstreams[gop].size()) - e->au_at[(size_t)k * e->G + gop];
+    if(e->hashes()) out->bytes -= SIGNATURE_SEI_BYTES; // (the application's Bits do not count the signature unit that closes the access unit)
     for(int c = 0; c < 3; c++) { // find_psnr_16bit (app/xeve_app_util.h:660-681)
         out->sse[c] = e->h_sums[at + (size_t)gop * 3 + c];
         const double factor = (double)((1 << (BIT_DEPTH - 8)) * (1 << (BIT_DEPTH - 8))), mse = (double)out->sse[c] / ((double)e->P.w * e->P.h / (c ? 4 : 1));
         out->psnr[c] = mse == 0.0 ? 100. : fabs(10 * log10((255 * 255 * factor) / mse));
     }
+    return XEVE_HIP_OK;
+}
+static_assert(XEVE_HIP_SIGNATURE_SEI_BYTES == SIGNATURE_SEI_BYTES, "the signature unit's size");
+extern "C" int xeve_hip_enc_signature(xeve_hip_enc *e, int gop, int frame, uint8_t out[48])
+{
+    XH_ENTER();
+    XH_REQUIRE(e && out);
+    if(!e->hashes()) { xh_set_error("xeve_hip_enc_signature: the run was created without reserved[0] bit 4 (hash)"); return XEVE_HIP_ERR_ARG; }
+    if(served_position(e, "xeve_hip_enc_signature", gop, frame) < 0) return XEVE_HIP_ERR_ARG;
+    e->copy_digests(frame, gop, out); // (a served picture's digests are on the host: the frame loop waited for them to write its signature unit)
     return XEVE_HIP_OK;
 }
 extern "C" int xeve_hip_enc_recon(xeve_hip_enc *e, int gop, int frame, void *dst, int on_device)

@@ -23,15 +23,17 @@ def stats_line(p):
 
 
 def config(w, h, qp=32, keyint=0, bframes=15, closed_gop=False, preset="medium", threads=1, fps=(30, 1), ref=0, always_second_pass=False, input_depth=8, level_idc=40, sei_info=True,
-           inter_slice_type=0, qp_cb_offset=0, qp_cr_offset=0, measure=False, keep_recon=False):
+           inter_slice_type=0, qp_cb_offset=0, qp_cr_offset=0, measure=False, keep_recon=False, hash=False):
     """the options of the reference application (xeve_app: -w -h -q -I -b --closed-gop --preset -m -z --ref -d; --inter-slice-type 0 B / 1 P, --qp-cb-offset,
     --qp-cr-offset as the reference LIBRARY takes them) as the library's configuration record.  measure: per-picture SSE / PSNR (BatchEncoder.pictures);
-    keep_recon: the reconstructed pictures stay on the device (BatchEncoder.recon; w * h * 3 bytes per picture of the batch) -- neither changes the bitstream"""
+    keep_recon: the reconstructed pictures stay on the device (BatchEncoder.recon; w * h * 3 bytes per picture of the batch) -- neither changes the bitstream.
+    hash: the application's --hash -- a 56-byte picture-signature SEI with the MD5 of each decoded plane behind every picture (BatchEncoder.signatures), hash=1 in the
+    option SEI; the digests are made on the device"""
     c = _lib.EncConfig()
     c.w, c.h, c.fps_num, c.fps_den, c.qp, c.keyint, c.bframes, c.closed_gop = w, h, fps[0], fps[1], qp, keyint, bframes, int(bool(closed_gop))
     c.preset, c.threads, c.inter_slice_type, c.ref = PRESETS[preset] if isinstance(preset, str) else int(preset), threads, int(inter_slice_type), ref
     c.reserved[2], c.reserved[3] = int(qp_cb_offset), int(qp_cr_offset)
-    c.reserved[0] = (1 if always_second_pass else 0) | (0 if sei_info else 2) | (4 if measure else 0) | (8 if keep_recon else 0) | ((int(level_idc) & 0xFF) << 8)  # (--info 0, --level-idc)
+    c.reserved[0] = (1 if always_second_pass else 0) | (0 if sei_info else 2) | (4 if measure else 0) | (8 if keep_recon else 0) | (16 if hash else 0) | ((int(level_idc) & 0xFF) << 8)  # (--info 0, --level-idc)
     c.reserved[1] = int(input_depth)
     return c
 
@@ -120,11 +122,25 @@ class BatchEncoder:
         """the application's table row of one picture (config(measure=True)) -- xeve_hip_enc_picture_info; raises for a picture whose access unit is not in the bitstream yet"""
         p = _lib.EncPicture()
         _lib.check(self._L.xeve_hip_enc_picture_info(self._h, int(gop), int(frame), C.byref(p)))
-        return {"frame": p.frame, "poc": p.poc, "type": SLICE_TYPES[p.slice_type], "tid": p.tid, "qp": p.qp, "idr": bool(p.idr), "coding_pos": p.coding_pos, "bytes": int(p.bytes),
-                "sse": [int(v) for v in p.sse], "psnr": [float(v) for v in p.psnr]}
+        row = {"frame": p.frame, "poc": p.poc, "type": SLICE_TYPES[p.slice_type], "tid": p.tid, "qp": p.qp, "idr": bool(p.idr), "coding_pos": p.coding_pos, "bytes": int(p.bytes),
+               "sse": [int(v) for v in p.sse], "psnr": [float(v) for v in p.psnr]}
+        if self.cfg.reserved[0] & 16:  # (bytes stays the application's Bits / 8: the signature unit is not counted)
+            row["md5"] = [d.hex() for d in self.signatures(gop, frame)]
+        return row
+
+    def signatures(self, gop, frame=None):
+        """the MD5 of the decoded Y, U and V plane (config(hash=True)) -- what the picture's signature SEI carries and hashlib.md5 gives for the planes of recon(): three
+        16-byte digests of one frame, or with frame=None a list of those for every frame in display order; raises for a picture whose access unit is not in the bitstream yet"""
+        out = []
+        for f in (range(self.frames) if frame is None else [int(frame)]):
+            buf = (C.c_uint8 * 48)()
+            _lib.check(self._L.xeve_hip_enc_signature(self._h, int(gop), f, buf))
+            out.append([bytes(buf[16 * c:16 * c + 16]) for c in range(3)])
+        return out if frame is None else out[0]
 
     def pictures(self, gop):
-        """every picture of one GOP in display order (a list of dicts: frame, poc, type 'I' / 'P' / 'B', tid, qp, idr, coding_pos, bytes, sse[3], psnr[3])"""
+        """every picture of one GOP in display order (a list of dicts: frame, poc, type 'I' / 'P' / 'B', tid, qp, idr, coding_pos, bytes, sse[3], psnr[3]; with
+        config(hash=True) also md5: the three planes' digests as hex)"""
         return [self.picture(gop, f) for f in range(self.frames)]
 
     def recon(self, gop, frame=None):
@@ -170,6 +186,39 @@ class walk_select:
         L = _lib.load()
         L.xeve_hip_walk_select(self.before), L.xeve_hip_walk_team(self.team_before), L.xeve_hip_walk_side(self.side_before)
         return False
+
+
+def signature_sei(tid, digests):
+    """the 56-byte picture-signature SEI NAL unit of --hash for a temporal id and three 16-byte digests (Y, U, V) -- xeve_hip_signature_sei; no device call"""
+    d = b"".join(bytes(x) for x in digests)
+    assert len(d) == 48
+    out = (C.c_uint8 * _lib.SIGNATURE_SEI_BYTES)()
+    n = _lib.load().xeve_hip_signature_sei(int(tid), d, out, len(out))
+    if n != _lib.SIGNATURE_SEI_BYTES:
+        raise _lib.XeveHipError("libxeve_hip rc=%d: %s" % (n, _lib.last_error()))
+    return bytes(out)
+
+
+def split_nal_units(bitstream):
+    """[(nal unit type, temporal id, payload behind the two header bytes)] of a bitstream as the encoder writes it: every unit behind a 4-byte big-endian length
+    (xeve_eco_nal_unit_len).  Raises unless the units consume the bitstream exactly.  Types: 0 non-IDR slice, 1 IDR slice, 24 SPS, 25 PPS, 28 SEI."""
+    units, at, n = [], 0, len(bitstream)
+    while at < n:
+        if at + 4 > n:
+            raise ValueError("a NAL unit's length field is cut short at byte %d" % at)
+        size = int.from_bytes(bitstream[at:at + 4], "big")
+        if size < 2 or at + 4 + size > n:
+            raise ValueError("the NAL unit at byte %d says %d bytes; %d are left" % (at, size, n - at - 4))
+        head = int.from_bytes(bitstream[at + 4:at + 6], "big")  # forbidden_zero_bit, nal_unit_type_plus1 (6), nuh_temporal_id (3), reserved (5), extension (1)
+        units.append((((head >> 9) & 0x3F) - 1, (head >> 6) & 7, bytes(bitstream[at + 6:at + 4 + size])))
+        at += 4 + size
+    return units
+
+
+def read_signatures(bitstream):
+    """[(temporal id, [md5 of Y, of U, of V])] per picture, in coding order, from the picture-signature SEI units of a bitstream coded with --hash (payload type 0x10, the
+    size byte 0x10, three 16-byte digests); a bitstream without them gives an empty list"""
+    return [(tid, [p[2 + 16 * c:18 + 16 * c] for c in range(3)]) for nut, tid, p in split_nal_units(bitstream) if nut == 28 and len(p) == 50 and p[:2] == b"\x10\x10"]
 
 
 def footprint(cfg, ngops, frames):
@@ -244,14 +293,15 @@ def encode_gops(cfg, ngops, frames, feed, free_bytes=None, max_batches=3, batch_
     return out
 
 
-def encode_file(yuv_path, out_path, cfg, gops, frames, max_batches=3, recon_path=None, stats_path=None):
+def encode_file(yuv_path, out_path, cfg, gops, frames, max_batches=3, recon_path=None, stats_path=None, hash=False):
     """the whole sequence: GOP g = frames [g * frames, (g + 1) * frames) of the file; the concatenated bitstreams are what the reference writes for the same sequence
     with --closed-gop -I frames.  Sequences beyond one batch are cut into batches that run side by side (encode_gops).  recon_path: the reconstructed
     sequence, GOP after GOP in display order -- the reference's -r file of the same run; stats_path: one line per picture as the application's table prints it (POC Tid
-    Ftype QP PSNR-Y PSNR-U PSNR-V Bits), every GOP in coding order.  Either switches the configuration's measure / keep_recon on for this call."""
-    if recon_path or stats_path:
+    Ftype QP PSNR-Y PSNR-U PSNR-V Bits), every GOP in coding order.  Either switches the configuration's measure / keep_recon on for this call.  hash: the
+    application's --hash for this call (a configuration made with config(hash=True) has it already); the table's Bits stay what they are without it."""
+    if recon_path or stats_path or hash:
         c = _lib.EncConfig.from_buffer_copy(cfg)
-        c.reserved[0] |= (8 if recon_path else 0) | (4 if stats_path else 0)
+        c.reserved[0] |= (8 if recon_path else 0) | (4 if stats_path else 0) | (16 if hash else 0)
         cfg = c
     fb = cfg.w * cfg.h * 3 // 2 * (2 if cfg.reserved[1] > 8 else 1)
     recon_file, stats_file = open(recon_path, "wb") if recon_path else None, open(stats_path, "w") if stats_path else None

@@ -53,6 +53,14 @@ class EncPicture(C.Structure):  # xeve_hip_enc_picture (88 B)
     _fields_ = [(n, C.c_int32) for n in "frame poc slice_type tid qp idr coding_pos reserved".split()] + [("bytes", C.c_uint64), ("sse", C.c_uint64 * 3), ("psnr", C.c_double * 3)]
 
 
+class Md5Job(C.Structure):  # xeve_hip_md5_job (24 B)
+    _fields_ = [("offset", C.c_int64), ("stride", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("reserved", C.c_int32)]
+
+
+MD5_JOB_DTYPE = [("offset", "<i8"), ("stride", "<i4"), ("w", "<i4"), ("h", "<i4"), ("reserved", "<i4")]
+SIGNATURE_SEI_BYTES = 56  # XEVE_HIP_SIGNATURE_SEI_BYTES
+
+
 class InterParams(C.Structure):  # xeve_hip_inter_params
     _fields_ = [("rdo", RdoParams), ("me", EpzsParams), ("refi_bits", (C.c_int32 * 8) * 2), ("range_recentre", (C.c_int32 * 8) * 2), ("max_cand", C.c_int32),
                 ("poc", C.c_int32), ("col_list_poc0", C.c_int32), ("pad_", C.c_int32), ("skip_th", C.c_double)]
@@ -277,6 +285,10 @@ FUNCTIONS = {
     "xeve_hip_enc_picture_info": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "xeve_hip_enc_recon": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),
     "xeve_hip_recon_measure": (c_int, [c_void_p, c_int, c_int, c_i64, c_i64, c_void_p, c_int, c_int, c_i64, c_i64, c_int, c_int, c_int, c_void_p, c_i64, c_void_p, c_void_p]),
+    # the application's --hash: decoded-picture MD5s made on the device, the picture-signature SEI
+    "xeve_hip_md5_planes": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "xeve_hip_enc_signature": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "xeve_hip_signature_sei": (c_int, [c_int, c_void_p, c_void_p, C.c_size_t]),
 }
 TABLES = {
     "xeve_tbl_sad_16b_hip": FN_SAD * 64,
