@@ -700,9 +700,11 @@ void xo_me_spel_pattern(const xo_pel *org0, int s_org, const xo_pel *org_bi, con
     for(int stage = 0; stage < 2; stage++) {
         const int cnt = stage ? p->qpel_cnt : p->hpel_cnt;
         const int8_t(*pat)[2] = stage ? pat_qpel : pat_hpel;
-        const int cx = mvx + (job->x << 2), cy = mvy + (job->y << 2); /* centre of this stage: picture coordinates, quarter pel */
+        /* centre of this stage: picture coordinates, quarter pel.  s16 in the reference (cx, cy, mv_x, mv_y, xeve_pinter.c:569): a vector the integer search
+           brought back from the picture's left end after a wrapped start has wrapped itself, and wraps back here */
+        const int cx = (int16_t)(mvx + (job->x << 2)), cy = (int16_t)(mvy + (job->y << 2));
         for(int i = 0; i < cnt; i++) {
-            const int mx = cx + pat[i][0], my = cy + pat[i][1];
+            const int mx = (int16_t)(cx + pat[i][0]), my = (int16_t)(cy + pat[i][1]);
             int bits = xo_mv_bits(mx - job->gmvp[0], my - job->gmvp[1]) + p->refi_bits;
             if(p->bi) bits += p->extra_bits;
             uint32_t cost = (uint32_t)(p->lambda_mv * (uint32_t)bits + (1u << 15)) >> 16;
@@ -711,7 +713,7 @@ void xo_me_spel_pattern(const xo_pel *org0, int s_org, const xo_pel *org_bi, con
             const int sad = xo_sad(w, h, org, pred, so, w, bit_depth);
             cost += (uint32_t)(p->bi ? sad >> 1 : sad);
             if(cost < cost_best) {
-                mvx = mx - (job->x << 2), mvy = my - (job->y << 2), cost_best = cost;
+                mvx = (int16_t)(mx - (job->x << 2)), mvy = (int16_t)(my - (job->y << 2)), cost_best = cost; /* (mv[] is an s16 as well, :632-633) */
                 if(stage) best_bits = bits; /* only the quarter-pel loop records the bits, xeve_pinter.c:683 */
             }
         }
@@ -758,16 +760,18 @@ void xo_me_raster(const xo_pel *org0, int s_org, const xo_pel *ref0, int s_ref, 
     for(int i = range[1]; i <= range[3]; i += st * (refi + 1))
         for(int j = range[0]; j <= range[2]; j += st * (refi + 1)) {
             const uint32_t c = me_cand_cost(org0, s_org, NULL, ref0, s_ref, x, y, j, i, gmvp, log2w, log2h, bit_depth, p, &bits);
-            if(c < cost_best) mvx = (j - x) << 2, mvy = (i - y) << 2, cost_best = c, best_bits = bits;
+            if(c < cost_best) mvx = (int16_t)((j - x) << 2), mvy = (int16_t)((i - y) << 2), cost_best = c, best_bits = bits; /* mv[] is an s16 (:212-213) */
         }
     for(int ss = ((refi + 1) * st) >> 1; ss > 0; ss >>= 1) {
         const int cx = mvx, cy = mvy;
         for(int i = -ss; i <= ss; i += ss)
             for(int j = -ss; j <= ss; j += ss) {
-                const int mx = (cx >> 2) + x + j, my = (cy >> 2) + y + i;
+                /* from the s16 vector, not from the position it was made of (:233-234): the vector of a position at the picture's left end, seen from the last CTU
+                   column of a picture wider than 8128, has wrapped, the centre lies right of every range and the grids find nothing */
+                const int mx = (int16_t)((cx >> 2) + x + j), my = (int16_t)((cy >> 2) + y + i);
                 if(mx < range[0] || mx > range[2] || my < range[1] || my > range[3]) continue;
                 const uint32_t c = me_cand_cost(org0, s_org, NULL, ref0, s_ref, x, y, mx, my, gmvp, log2w, log2h, bit_depth, p, &bits);
-                if(c < cost_best) mvx = (mx - x) << 2, mvy = (my - y) << 2, cost_best = c, best_bits = bits;
+                if(c < cost_best) mvx = (int16_t)((mx - x) << 2), mvy = (int16_t)((my - y) << 2), cost_best = c, best_bits = bits;
             }
     }
     res->mv[0] = (int16_t)mvx, res->mv[1] = (int16_t)mvy, res->cost = cost_best, res->beststep = 0, res->best_mv_bits = best_bits;
@@ -796,9 +800,20 @@ uint32_t xo_me_epzs(const xo_pel *org0, int s_org, const xo_pel *org_bi, const x
     return xo_me_epzs_mot(org0, s_org, org_bi, ref0, s_ref, x, y, mvp, mv, log2w, log2h, bit_depth, coef, p, &mot);
 }
 
+/* how many searches had a frame-coordinate predictor or start vector beyond an s16 (x << 2 reaches 32 736 in the last CTU column of an 8192-wide picture): the tests ask
+   whether an encode reached that zone */
+static long me_wrapped_searches;
+long xo_me_wrapped_searches(int reset)
+{
+    const long n = __atomic_load_n(&me_wrapped_searches, __ATOMIC_RELAXED);
+    if(reset) __atomic_store_n(&me_wrapped_searches, 0, __ATOMIC_RELAXED);
+    return n;
+}
+
 uint32_t xo_me_epzs_mot(const xo_pel *org0, int s_org, const xo_pel *org_bi, const xo_pel *ref0, int s_ref, int x, int y, const int16_t mvp[2],
                         int16_t mv[2], int log2w, int log2h, int bit_depth, const int16_t (*coef)[8], const xo_epzs_params *p, int *mot_bits)
 {
+    if(mvp[0] + (x << 2) > 32767 || (p->me.bi == 1 ? mv[0] : mvp[0]) + (x << 2) > 32767) __atomic_fetch_add(&me_wrapped_searches, 1, __ATOMIC_RELAXED);
     xo_me_params me = p->me;
     xo_me_job    job;
     xo_me_result r;

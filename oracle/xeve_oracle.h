@@ -162,6 +162,7 @@ void xo_me_spel_pattern(const xo_pel *org0, int s_org, const xo_pel *org_bi, con
 
 /* me_raster (xeve_pinter.c:158-268): grid of step max(5, S / 2) * (refi + 1) over the range, then 3x3 grids of halving step around the best;
  * me_ipel_refinement (:270-361): the nine integer positions around mvi.  Both: cost, mv (relative, quarter pel), best_mv_bits in *res. */
+long xo_me_wrapped_searches(int reset); /* searches whose frame-coordinate predictor or start vector did not fit an s16, since the last reset */
 void xo_me_raster(const xo_pel *org0, int s_org, const xo_pel *ref0, int s_ref, int x, int y, const int16_t range[4], const int16_t gmvp[2], int log2w, int log2h,
                   int bit_depth, const xo_me_params *p, int refi, xo_me_result *res);
 void xo_me_ipel_refinement(const xo_pel *org0, int s_org, const xo_pel *org_bi, const xo_pel *ref0, int s_ref, int x, int y, const int16_t range[4],

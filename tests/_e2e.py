@@ -120,6 +120,8 @@ def make_yuv(path, w, h, frames, seed):
             for (pw, ph, sc, base) in ((w, h, 1.0, 128.0), (w // 2, h // 2, 2.0, 110.0), (w // 2, h // 2, 2.0, 140.0)):
                 yy, xx = np.mgrid[0:ph, 0:pw].astype(np.float64) * sc
                 xs, ys = (xx + 3.0 * t, yy + 2.0 * t) if seed < 6000 else (xx + 23.0 * t, yy + 17.0 * t)  # (seeds from 6000: jumps the first search only finds on its far rings)
+                if 7000 <= seed < 8000:  # a pan: 23 samples per frame along the rows, one across -- the vectors towards the past point 23 samples right even in a strip 8 rows high
+                    xs, ys = xx + 23.0 * t, yy + 1.0 * t
                 a = base + 60 * np.sin(xs / 9.0) * np.cos(ys / 7.0) + 30 * np.sin((xs + ys) / 13.0) + 12 * np.sin(xs / 3.0)
                 a[ph // 2:, :] += 25 * np.sin((xx[ph // 2:, :] - 5.0 * t) / 6.0)  # a second motion in the lower half
                 f.write(np.clip(a + r.integers(-2, 3, size=a.shape), 0, 255).astype(np.uint8).tobytes())

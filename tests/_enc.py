@@ -292,6 +292,31 @@ PICTURE_SIZE_CASES = {
 PICTURE_SIZE_HOST_CASES = dict(
     [("size_%dx%d_moving_host" % (w, h), (w, h, 1, 4, 5021, _SIZE_A, 1)) for w, h in ((16, 8), (8, 24), (32, 32), (40, 72), (72, 40), (208, 80))] +
     [("size_%dx%d_noise_m2_host" % (w, h), (w, h, 1, 3, 21, _SIZE_B, 2)) for w, h in ((144, 152), (168, 176), (184, 136))])
+# The upper end of the accepted set (Param::finish takes up to 8192x4320), as strips: the cost is the number of CTU steps, not the area.  Beyond 8128 samples of width the
+# reference's s16 quarter-pel frame coordinates wrap in the last CTU column when a predictor or start vector points right (tests/_me_cases.py, the right-edge family):
+# seed 7061 is the texture panning 23 samples per frame along the rows (tests/_e2e.py), so that the vectors towards the past point 23 samples right.  tests/test_enc_host.py asserts with the oracle's
+# counter which cases reach the zone.  The tall strips: 68 CTU rows, the last one 32 high, on one row chain and on eight (nine rounds of the wavefront).
+LARGEST_SIZE_CASES = {
+    "largest_8128x8_control": (8128, 8, 1, 3, 7061, _SIZE_B, 1),  # the widest picture in which nothing can wrap
+    # 128 CTUs, the last one 8 samples wide, above 8128: the smallest picture with a CU (x = 8128) whose x << 2 = 32 512 leaves room for a wrap.  This clip cannot get
+    # there, and the test asserts that it does not: the wrap needs a predictor of 32 768 - 32 512 = 256 quarter pel = 64 samples.  The picture's 16 rows allow CUs of at most
+    # 16, so the CUs the one at x = 8128 takes its candidates from start at x >= 8112, and a vector SEARCHED there is at most 4 * (8135 - 8112) + 3 = 95 (the integer search
+    # is clipped to w - 1, xeve_pinter.c:2126).  256 or more can only be a vector searched at x <= 8071 and inherited unsearched (skip, direct, the temporal candidate scaled
+    # by at most 2 here) across the four CUs between -- and the content moves 23 samples per frame with the references one and two frames back: no displacement beyond
+    # 46 samples = 184 quarter pel exists to be found, 32 512 + 184 < 32 767.  (Pans of 56 to 70 samples per frame, periodic, non-periodic and fading to flat towards the
+    # edge, were tried: the fast low-delay search, range 64 and three empty rings to stop, never follows them.)  The case holds the geometry to the reference's bytes
+    "largest_8136x16_ldb": (8136, 16, 1, 3, 7061, _SIZE_B, 1),
+    "largest_8192x8_ldb": (8192, 8, 1, 3, 7061, _SIZE_B, 1),  # one CU row, 128 CTUs
+    "largest_8192x64_closed": (8192, 64, 1, 2, 7061, ["--preset", "medium", "--closed-gop", "-I", "8"], 1),  # every CU size in the last CTU
+    "largest_8192x8_slow": (8192, 8, 1, 2, 7061, ["--preset", "slow", "--closed-gop", "-I", "8"], 1),  # quarter pel (the fused walk only)
+    "largest_8192x8_placebo": (8192, 8, 1, 2, 7061, ["--preset", "placebo", "--closed-gop", "-I", "8"], 1),  # the raster search, 8 + 8 sub-pel points (the fused walk only)
+    "largest_72x4320": (72, 4320, 1, 2, 7061, ["--preset", "medium", "--closed-gop", "-I", "8"], 1),
+    "largest_136x4320_m8": (136, 4320, 1, 2, 7061, ["--preset", "medium", "--closed-gop", "-I", "8"], 8),
+}
+# the cases whose clip reaches the zone: the last CU column's x << 2 plus the clip's largest displacement (23 samples per frame, references at most two frames away:
+# 184 quarter pel) passes 32 767 -- the 8192-wide ones
+LARGEST_SIZE_IN_ZONE = tuple(n for n, c in LARGEST_SIZE_CASES.items() if ((c[0] - 8) << 2) + 4 * 46 > 32767)
+assert LARGEST_SIZE_IN_ZONE == ("largest_8192x8_ldb", "largest_8192x64_closed", "largest_8192x8_slow", "largest_8192x8_placebo")
 # What the PRODUCT library's configuration check (enc_plan.h Param::finish) takes and what it refuses -- ONE table, read by tests/test_enc_host.py through
 # xeve_hip_enc_footprint (no device: a change of the accepted set fails in the build container) and by tests/test_enc_gpu.py through xeve_hip_enc_create.
 # (kwargs of xeve_amd.encode.config beside w / h, accepted?)
@@ -311,6 +336,8 @@ CONFIG_ACCEPTANCE = [
     (dict(w=128, h=64, bframes=0, keyint=0, closed_gop=True), False),
     # pictures below one CTU and with partial CTUs (PICTURE_SIZE_CASES code them): the accepted set must not be narrowed quietly
     (dict(w=8, h=8), True), (dict(w=200, h=8), True), (dict(w=8, h=64), True), (dict(w=176, h=144, threads=2), True),
+    # the upper end (LARGEST_SIZE_CASES code strips of it); both readers of this table size one GOP of two pictures: nothing of the full area is created on a device
+    (dict(w=8192, h=8), True), (dict(w=8, h=4320), True), (dict(w=8, h=4328), False),
 ]
 
 

@@ -184,3 +184,27 @@ def fuzz_cases(n_iter, seed0=0, n_jobs=36):
                 jobs["mvp"][:] = jobs["mvp"][:, :, :1]
                 jobs["mvp"][: len(jobs) // 2] = 0
             yield refs, org, st, P, jobs, dict(it=it, lw=lw, kind=kind, w=w, h=h, bd=bd, idc=idc, slice_type=st_type, nref=nref)
+
+
+# ---- CUs in the last CTU of an 8192-wide picture: quarter-pel frame coordinates of predictors and start vectors pass an s16 (see _me_cases' right-edge family) -------------
+RIGHT_EDGE_W, RIGHT_EDGE_H = 8192, 64
+
+
+def make_right_edge_inter_jobs(r, n, cu, nstates, refs, slice_type):
+    """make_inter_jobs in the last CTU of a RIGHT_EDGE_W x RIGHT_EDGE_H picture: two jobs of three in its last CU column, the others anywhere in it; the x component of
+    three neighbour vectors of four points 0 to 63 samples right (the fourth stays what make_inter_jobs drew: the true motion, noise or 1)"""
+    w, h = RIGHT_EDGE_W, RIGHT_EDGE_H
+    j = make_inter_jobs(r, n, w, h, cu, nstates, refs, slice_type)
+    col = r.integers(0, 64 // cu, size=n)
+    col[np.arange(n) % 3 != 2] = 64 // cu - 1
+    j["x"] = w - 64 + col * cu
+    right = r.integers(0, 253, size=(n, 2, 4))
+    keep = r.integers(0, 4, size=(n, 2, 1)) == np.arange(4).reshape(1, 1, 4)
+    j["mvp"][..., 0] = np.where(keep, j["mvp"][..., 0], right)
+    return j
+
+
+def right_edge_wrapped(jobs, slice_type):
+    """per job: a neighbour vector of a list in use whose frame coordinate (x << 2) + mv_x does not fit an s16 -- pinter_me_epzs' gmvp / mvi for it wrap"""
+    lists = 2 if slice_type == 0 else 1
+    return ((jobs["x"].astype(np.int64)[:, None, None] << 2) + jobs["mvp"][:, :lists, :, 0] > 32767).any(axis=(1, 2))

@@ -413,3 +413,134 @@ def batch_launches(S, bi, textured):
 BATCH_STEPS = {(8, 0, False): 3, (16, 0, False): 4, (32, 0, False): 6, (64, 0, False): 4, (8, 1, False): 1, (16, 1, False): 1, (32, 1, False): 1, (64, 1, False): 1,
                (8, 2, False): 3, (16, 2, False): 3, (32, 2, False): 5, (64, 2, False): 5, (8, 0, True): 5, (16, 0, True): 5, (32, 0, True): 6, (64, 0, True): 5,
                (8, 1, True): 1, (16, 1, True): 1, (32, 1, True): 1, (64, 1, True): 1, (8, 2, True): 5, (16, 2, True): 3, (32, 2, True): 4, (64, 2, True): 7}
+
+
+# ---- the right edge of the widest accepted picture: quarter-pel FRAME coordinates beyond an s16 ----------------------------------------------------------------------
+# pinter_me_epzs keeps gmvp = mvp + (x << 2) and mvi = start + (x << 2) in s16 (xeve_pinter.c:711-735, 790-791, 841-842).  x << 2 reaches 32 736 at x = 8184, so in
+# the last CTU column of a picture wider than 8128 a predictor or start vector that points right wraps: the wrapped gmvp prices every candidate against a point 16 384
+# samples to the left, and a wrapped mvi starts the diamond at min_clip -- its first round has no candidate inside the range, the range is re-centred there, and the
+# whole search happens at the picture's LEFT end.  Deterministic C on the reference's side, mirrored by casts in the oracle, me.hip and walk_inter.h; this family
+# executes them with values that wrap.
+#   planes    8192 x 64 plus padding; the reference plane an integer texture (closed form, no generator state: the fixture stores a CRC, not the samples), the original
+#             of size S the reference moved RE_SHIFT[S] samples plus a little noise, so the true motion points right
+#   jobs      y = 0, x = 8192 - S for S = 64 / 32 / 16 / 8, five predictors per size: (x << 2) + mvp_x = 32 764, 32 767 (controls), 32 768, 32 800, 33 500
+#   modes     bi 0, 1 (BI_NORMAL: starts from mv), 2 (starts from mvp)
+#   ranges    xeve_pinter.c:2124-2126 for w = 8192, h = 64; RE_PRESETS: search ranges and sub-pel counts of presets fast, medium, slow (quarter pel) and placebo (raster)
+# The twin of a job is the same search RE_TWIN samples further left on the same content (the planes rolled by RE_TWIN columns, x and max_clip RE_TWIN less): every sample, every
+# clip distance and every vector is the same, only x << 2 is 4 * RE_TWIN less and nothing wraps -- what the wrapped job would give in int arithmetic.
+RE_W, RE_H = 8192, 64
+RE_SIZES = (64, 32, 16, 8)
+RE_SHIFT = {64: 40, 32: 25, 16: 12, 8: 5}
+RE_TARGETS = (32764, 32767, 32768, 32800, 33500)
+RE_WRAPPED_PER_LAUNCH = 3  # of 5 jobs: the targets beyond 32 767
+RE_PRESETS = {"fast": dict(msr=32, sr=16, hpel_cnt=2, qpel_cnt=0, raster=0), "medium": dict(msr=64, sr=32, hpel_cnt=4, qpel_cnt=0, raster=0),
+              "slow": dict(msr=128, sr=64, hpel_cnt=4, qpel_cnt=4, raster=0), "placebo": dict(msr=384, sr=96, hpel_cnt=8, qpel_cnt=8, raster=1)}
+RE_LAUNCHES = [(S, bi, preset) for S in RE_SIZES for bi in (0, 1, 2) for preset in RE_PRESETS]
+RE_TWIN = 256  # (64 would do for the targets up to 32 800; 33 500 - 4 * 64 still wraps)
+
+
+def s16(v):
+    return ((int(v) + 32768) & 0xFFFF) - 32768
+
+
+def _tri(v, p):
+    return np.abs(v % (2 * p) - p)
+
+
+@functools.lru_cache(maxsize=None)
+def right_edge_ref_plane():
+    yy, xx = np.mgrid[0:RE_H + 2 * PAD, 0:RE_W + 2 * PAD].astype(np.int64)
+    v = 100 + 5 * _tri(xx + yy, 53) + 4 * _tri(2 * xx - yy, 37) + 3 * _tri(xx + 3 * yy, 11) + ((((xx * 73856093) ^ (yy * 19349663)) >> 5) & 7)
+    return np.ascontiguousarray(v.astype(np.int16))
+
+
+@functools.lru_cache(maxsize=None)
+def right_edge_planes(S, twin=False):
+    """the plane pair of size S; twin: both planes rolled RE_TWIN columns to the left, so that the block at x - RE_TWIN sees what the block at x saw"""
+    ref = right_edge_ref_plane()
+    yy, xx = np.mgrid[0:ref.shape[0], 0:ref.shape[1]].astype(np.int64)
+    org = np.roll(ref, -RE_SHIFT[S], axis=1) + ((((xx * 83492791) ^ (yy * 2971215073)) >> 7) % 5 - 2).astype(np.int16)  # org(u) = ref(u + shift) + noise
+    if twin:
+        org, ref = np.roll(org, -RE_TWIN, axis=1), np.roll(ref, -RE_TWIN, axis=1)
+    return dict(org=np.ascontiguousarray(org), ref=np.ascontiguousarray(ref), s=ref.shape[1], W=RE_W, H=RE_H)
+
+
+def right_edge_jobs(S, bi, preset, twin=False):
+    """the five jobs of one launch as diamond cases (gmvp and mvi as pinter_me_epzs hands them down: wrapped), with the raw mvp / mv0 and the sub-pel counts beside them"""
+    pl, pr = right_edge_planes(S, twin), RE_PRESETS[preset]
+    off = RE_TWIN if twin else 0
+    x, y = RE_W - S - off, 0
+    mn, mx = (-127, -127), (RE_W - 1 - off, RE_H - 1)
+    k = RE_SIZES.index(S) * 12 + bi * 4 + list(RE_PRESETS).index(preset)
+    lambda_mv, mot_other, sr = (1 << 17) + 9001 * k, 3 + k % 17, (5 if bi == 1 else pr["sr"])
+    blk = pl["org"][PAD:PAD + S, PAD + x:PAD + x + S].astype(np.int32).reshape(-1)
+    cases = []
+    for t, target in enumerate(RE_TARGETS):
+        mvp = (target - ((RE_W - S) << 2), 4 * (t - 2) + 1)
+        mv0 = ((mvp[0] >> 2) << 2, (mvp[1] >> 2) << 2)
+        start = mv0 if bi == 1 else mvp
+        cx, cy = _clip(x + (start[0] >> 2), mn[0], mx[0]), _clip(y + (start[1] >> 2), mn[1], mx[1])
+        rng = [_clip(cx - sr, mn[0], mx[0]), _clip(cy - sr, mn[1], mx[1]), _clip(cx + sr, mn[0], mx[0]), _clip(cy + sr, mn[1], mx[1])]
+        org_bi = (blk + (np.arange(S * S) * 7 + 3 * t + k) % 5 - 2).astype(np.int16)  # 2 * original - the other list's prediction, where that prediction is good
+        cases.append(dict(org=pl["org"], ref=pl["ref"], s=pl["s"], x=x, y=y, S=S, bi=bi, min_clip=mn, max_clip=mx, range=rng,
+                          gmvp=(s16(mvp[0] + (x << 2)), s16(mvp[1] + (y << 2))), mvi=(s16(start[0] + (x << 2)), s16(start[1] + (y << 2))), msr=pr["msr"], sr=sr,
+                          lambda_mv=lambda_mv, faststep=3, mot_other=mot_other, org_bi=org_bi, beststep_in=0, mvp=mvp, mv0=mv0, hpel_cnt=pr["hpel_cnt"],
+                          qpel_cnt=pr["qpel_cnt"], raster=pr["raster"], frame_x=mvp[0] + (x << 2)))
+    return cases
+
+
+def right_edge_wrapped(c):
+    """(a) of the family: the job's quarter-pel frame coordinate does not fit an s16"""
+    return c["frame_x"] > 32767
+
+
+def right_edge_spel_case(c, mvi=None):
+    """the sub-pel pattern with the job's (wrapped) predictor around the integer vector of the true motion, or around mvi: the vector the job's diamond search ended
+    on -- from a wrapped start that is a position at the picture's left end whose s16 vector has wrapped too, and cx = mvi + (x << 2) wraps back (xeve_pinter.c:584)"""
+    return dict(org=c["org"], ref=c["ref"], s=c["s"], x=c["x"], y=c["y"], S=c["S"], bi=min(c["bi"], 1), gmvp=c["gmvp"], mvi=mvi or (4 * RE_SHIFT[c["S"]], 0), lambda_mv=c["lambda_mv"],
+                mot_other=c["mot_other"], org_bi=c["org_bi"], hpel_cnt=c["hpel_cnt"], qpel_cnt=c["qpel_cnt"])
+
+
+def right_edge_epzs_case(c, ipel=False):
+    """the whole pinter_me_epzs of the job: raw mvp and start vector, the casts are the search's own; ipel: the integer refinement in place of the sub-pel pattern"""
+    return dict(org=c["org"], ref=c["ref"], s=c["s"], x=c["x"], y=c["y"], S=c["S"], bi=min(c["bi"], 1), min_clip=c["min_clip"], max_clip=c["max_clip"], mvp=c["mvp"], mv0=c["mv0"],
+                msr=c["msr"], sr=c["sr"], lambda_mv=c["lambda_mv"], mot_other=c["mot_other"], org_bi=c["org_bi"], hpel_cnt=0 if ipel else c["hpel_cnt"],
+                qpel_cnt=0 if ipel else c["qpel_cnt"], raster=c["raster"], refi=0)
+
+
+def right_edge_crc():
+    import zlib
+
+    return [zlib.crc32(right_edge_ref_plane().tobytes())] + [zlib.crc32(right_edge_planes(S)["org"].tobytes()) for S in RE_SIZES]
+
+
+RE_JOBS, RE_WRAPPED = 240, 144  # 48 launches of 5 jobs; the 3 targets beyond 32 767 of each
+RE_SPEL_WRAPS = 140             # wrapped jobs whose diamond ends on a vector v with v + (x << 2) outside an s16 (counted on the reference's recorded results)
+
+
+def assert_right_edge_conditions(entries):
+    """entries: [((S, bi, preset), case, dia, twin_dia, epzs, twin_epzs)] of whole launches, the results being the reference's (or what is held to them).
+    (a) three jobs of five in every launch have (x << 2) + mvp_x > 32 767; (b) in every launch -- every size, mode and preset -- every one of them ends elsewhere or at
+    another cost than its twin, where nothing wraps, in the diamond and in the whole search (with the casts removed job and twin are one computation); the two controls
+    of each launch, 32 764 and 32 767, equal their twins, so the twin is a fair control"""
+    per = {}
+    for L, c, dia, tdia, ep, tep in entries:
+        n = per.setdefault(L, dict(jobs=0, wrapped=0, differ=0, control_differs=0))
+        n["jobs"] += 1
+        if right_edge_wrapped(c):
+            assert not -32768 <= c["frame_x"] <= 32767 and c["gmvp"][0] == c["frame_x"] - 65536
+            n["wrapped"] += 1
+            n["differ"] += dia != tdia and ep != tep
+        else:
+            assert c["gmvp"][0] == c["frame_x"]
+            n["control_differs"] += dia != tdia or ep != tep
+    for L, n in per.items():
+        assert n == dict(jobs=5, wrapped=RE_WRAPPED_PER_LAUNCH, differ=RE_WRAPPED_PER_LAUNCH, control_differs=0), (L, n)
+    wrapped = sum(n["wrapped"] for n in per.values())
+    assert 3 * wrapped >= sum(n["jobs"] for n in per.values())
+    return wrapped
+
+
+def spel_wraps(c, dia):
+    """the vector the diamond ended on, made a frame coordinate again (cx = mvi + (x << 2), xeve_pinter.c:584), does not fit an s16"""
+    return not -32768 <= dia[1] + (c["x"] << 2) <= 32767

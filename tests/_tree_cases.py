@@ -158,6 +158,18 @@ def make_inter_case(seed, w, h, bd, idc, slice_type, nref, odd_poc, skip_th, con
     return dict(refs=refs, org=org, mod=mod, maps=maps, col=col, P=P, ipar=ipar, entry=entry, idc=idc, w=w, h=h, order=order, ecu_depth=2 if odd_poc else 4, slice_type=slice_type, content=content)
 
 
+# the last three CTUs of an 8192 x 64 picture (the maps start empty: the first of them has no neighbours, the last two take their predictors from what was just coded);
+# the reference pictures of these seeds are shifted so that the vectors point 8 samples right, and CUs from x = 8176 on search from predictors whose frame coordinate
+# passes an s16: (seed, slice type, searches with a wrapped frame coordinate -- the oracle's counter, asserted by tests/test_walk_host.py)
+RIGHT_EDGE_INTER_CASES = [(4804, 1, 5), (4808, 0, 16)]
+
+
+def make_right_edge_inter_case(seed, slice_type):
+    c = make_inter_case(seed, 8192, 64, 10, 1, slice_type, 1, 0, 0.0)
+    c["order"] = c["order"][-3:]
+    return c
+
+
 def oracle_tree_any():
     L = oracle()
     L.xo_mode_analyze_ctu.restype = C.c_double

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Writes tests/golden/enc_v1.json from the UNMODIFIED reference application (oracle/_ref/xeveb_app).  Build container only.
   "plans":   per (options, frames) the table the application prints per coded picture -- POC, temporal id, slice type, QP, first reference picture of each list;
-  "batches": per case of tests/_enc.py BATCH_CASES(_REAL) (and the lists behind them, QP_RANGE_CASES, PICTURE_SIZE_CASES and SATURATED_CASES included) the md5 + size of every GOP's bitstream, each GOP coded as a run of its own (--seek g * F --frames F).
+  "batches": per case of tests/_enc.py BATCH_CASES(_REAL) (and the lists behind them, QP_RANGE_CASES, PICTURE_SIZE_CASES, SATURATED_CASES and LARGEST_SIZE_CASES included) the md5 + size of every GOP's bitstream, each GOP coded as a run of its own (--seek g * F --frames F).
 usage: make_enc_golden.py [plans] [case names ...] -- without arguments everything is (re)made."""
 import json
 import os
@@ -12,7 +12,7 @@ import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from _e2e import make_yuv  # noqa: E402
-from _enc import BATCH_CASES, BATCH_CASES_REAL, DEPTH10_CASES, GOLDEN, HEADER_OPTION_CASES, HOST_PINNED_CASES, PLACEBO_BATCH_CASES, PICTURE_SIZE_CASES, PICTURE_SIZE_HOST_CASES, PLAN_GRID, PRESET_REAL_CASES, QP_RANGE_CASES, SATURATED_CASES, SATURATED_REAL_CASES, SLOW_BATCH_CASES, WIDE_STACK_CASES, app_args_and_env, md5, widen10  # noqa: E402
+from _enc import BATCH_CASES, BATCH_CASES_REAL, DEPTH10_CASES, GOLDEN, HEADER_OPTION_CASES, HOST_PINNED_CASES, LARGEST_SIZE_CASES, PLACEBO_BATCH_CASES, PICTURE_SIZE_CASES, PICTURE_SIZE_HOST_CASES, PLAN_GRID, PRESET_REAL_CASES, QP_RANGE_CASES, SATURATED_CASES, SATURATED_REAL_CASES, SLOW_BATCH_CASES, WIDE_STACK_CASES, app_args_and_env, md5, widen10  # noqa: E402
 from _libs import REF_APP  # noqa: E402
 
 ROW = re.compile(r"^(?:\[.*?\] )*(\d+)\s+(\d+)\s+\((.)\)\s+(\d+)\s+[\d.]+\s+[\d.]+\s+[\d.]+\s+\d+\s+\d+\s*(.*)$")
@@ -57,7 +57,7 @@ with tempfile.TemporaryDirectory() as d:
                 assert len(rows) == n, (cli, n, rows)
                 out["plans"].append({"cli": cli, "frames": n, "rows": rows})
         print("plans:", len(out["plans"]))
-    for name, (w, h, gops, frames, seed, cli, threads) in list(BATCH_CASES.items()) + list(BATCH_CASES_REAL.items()) + list(DEPTH10_CASES.items()) + list(HOST_PINNED_CASES.items()) + list(HEADER_OPTION_CASES.items()) + list(SLOW_BATCH_CASES.items()) + list(PLACEBO_BATCH_CASES.items()) + list(PRESET_REAL_CASES.items()) + list(QP_RANGE_CASES.items()) + list(WIDE_STACK_CASES.items()) + list(PICTURE_SIZE_CASES.items()) + list(PICTURE_SIZE_HOST_CASES.items()) + list(SATURATED_CASES.items()) + list(SATURATED_REAL_CASES.items()):
+    for name, (w, h, gops, frames, seed, cli, threads) in list(BATCH_CASES.items()) + list(BATCH_CASES_REAL.items()) + list(DEPTH10_CASES.items()) + list(HOST_PINNED_CASES.items()) + list(HEADER_OPTION_CASES.items()) + list(SLOW_BATCH_CASES.items()) + list(PLACEBO_BATCH_CASES.items()) + list(PRESET_REAL_CASES.items()) + list(QP_RANGE_CASES.items()) + list(WIDE_STACK_CASES.items()) + list(PICTURE_SIZE_CASES.items()) + list(PICTURE_SIZE_HOST_CASES.items()) + list(SATURATED_CASES.items()) + list(SATURATED_REAL_CASES.items()) + list(LARGEST_SIZE_CASES.items()):
         if only and name not in only:
             continue
         yuv, evc = os.path.join(d, name + ".yuv"), os.path.join(d, name + ".evc")

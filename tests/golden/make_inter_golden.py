@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Writes tests/golden/inter_v1.npz: CUs with their neighbour vectors and what the reference's xeve_pinter_analyze_cu (src_base/xeve_pinter.c:1839-2047,
 via oracle/ref_rdo_driver.c: its own xeve_get_motion / xeve_get_mv_dir, pinter_me_epzs, check_best_mvp, analyze_bi, pinter_residue_rdo) returns for
-them -- cost, cu_mode, motion data, core->nnz, coefficients, reconstruction, core->s_next_best.  Fields the reference leaves stale are zeroed
+them -- cost, cu_mode, motion data, core->nnz, coefficients, reconstruction, core->s_next_best.  With the argument `right_edge`: tests/golden/inter_right_edge_v1.npz,
+the same for _inter_golden.RIGHT_EDGE_CASES (CUs in the last CTU of an 8192-wide picture).  Fields the reference leaves stale are zeroed
 (_inter_cases.mask_unobservable; coefficients of skipped CUs).  Pictures and coder states are regenerated from the recorded seed.  Build container only."""
 import os
 import sys
@@ -9,22 +10,19 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from _inter_cases import make_inter_jobs, make_inter_params, make_inter_picture, mask_unobservable  # noqa: E402
+from _inter_cases import mask_unobservable  # noqa: E402
 from _libs import INTER_RESULT_DTYPE, SBAC_DTYPE, ptr, ref_inter  # noqa: E402
 from _mc_cases import refpic_table  # noqa: E402
-from _rdo_cases import states  # noqa: E402
-from _inter_golden import CASES, N_JOBS  # noqa: E402
+from _inter_golden import CASES, RIGHT_EDGE_CASES, case_inputs  # noqa: E402
 
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "inter_v1.npz")
+RIGHT_EDGE = sys.argv[1:] == ["right_edge"]
+OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "inter_right_edge_v1.npz" if RIGHT_EDGE else "inter_v1.npz")
 R = ref_inter()
 d = {}
-for k, (seed, w, h, bd, nref, idc, st_type, lw, skip_th) in enumerate(CASES):
-    r = np.random.default_rng(seed)
-    refs, org = make_inter_picture(r, w, h, bd, nref, idc, st_type)
+for k, case in enumerate(RIGHT_EDGE_CASES if RIGHT_EDGE else CASES):
+    seed, w, h, bd, nref, idc, st_type, lw, skip_th = case
+    refs, org, st, P, jobs = case_inputs(case, RIGHT_EDGE)
     tab = refpic_table(refs, lambda a, off: int(a.ctypes.data) + 2 * off)
-    st = states(r, 6)
-    P = make_inter_params(r, lw, w, h, bd, nref, idc, st_type, refs, skip_th)
-    jobs = make_inter_jobs(r, N_JOBS, w, h, 1 << lw, len(st), refs, st_type)
     n0 = 1 << (2 * lw)
     nc = max(1, n0 >> (refs["ws"] + refs["hs"]))
     res, best = np.zeros(len(jobs), INTER_RESULT_DTYPE), np.zeros(len(jobs), SBAC_DTYPE)

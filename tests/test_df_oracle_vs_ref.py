@@ -10,7 +10,7 @@ pytestmark = pytest.mark.skipif(ref_df() is None, reason="oracle/_ref not built 
 
 
 @pytest.mark.parametrize("w,h,bd,idc,min_cu", [(128, 64, 10, 1, 4), (200, 136, 10, 1, 8), (64, 64, 8, 1, 4), (96, 72, 10, 0, 4), (72, 40, 12, 3, 4),
-                                               (320, 192, 10, 1, 8), (8, 8, 10, 1, 4)])
+                                               (320, 192, 10, 1, 8), (8, 8, 10, 1, 4), (8192, 8, 10, 1, 4), (8, 4320, 10, 1, 4)])  # (... strips of the widest and the tallest accepted picture)
 def test_deblock_picture(w, h, bd, idc, min_cu):
     O, R = oracle_df(), ref_df()
     r = np.random.default_rng(w * 7 + h + bd + idc)
@@ -54,11 +54,15 @@ def test_deblock_picture_with_tiles(w, h, sx, sy):
 def test_picbuf_expand():
     O, R = oracle_df(), ref_df()
     r = np.random.default_rng(3)
-    for (w, h, e) in [(64, 32, 16), (40, 24, 9), (8, 8, 16)]:
-        s = w + 2 * PAD
-        a = r.integers(0, 1024, size=(h + 2 * PAD, s)).astype(np.int16)
+    # (... and strips of the widest and the tallest accepted picture at the reference's own padding depths: luma 8192x8 / 8x4320 by 144, their chroma planes by 72 --
+    # what tests/test_hip_df.py holds the device's padding to)
+    for (w, h, e) in [(64, 32, 16), (40, 24, 9), (8, 8, 16), (8192, 8, 144), (8, 4320, 144), (4096, 4, 72), (4, 2160, 72)]:
+        pad = max(PAD, e)
+        s = w + 2 * pad
+        a = r.integers(0, 1024, size=(h + 2 * pad, s)).astype(np.int16)
         b = a.copy()
-        O.xo_picbuf_expand(ptr(a, PAD * s + PAD), s, w, h, e)
+        O.xo_picbuf_expand(ptr(a, pad * s + pad), s, w, h, e)
         z = np.zeros(4, np.int16)
-        R.refdrv_picbuf_expand(ptr(b, PAD * s + PAD), ptr(z), ptr(z), s, 0, w, h, 0, 0, e, 0, 0)
-        assert np.array_equal(a, b)
+        R.refdrv_picbuf_expand(ptr(b, pad * s + pad), ptr(z), ptr(z), s, 0, w, h, 0, 0, e, 0, 0)
+        assert np.array_equal(a, b), (w, h, e)
+        assert np.array_equal(a[pad - e:pad, pad:pad + w], np.tile(a[pad, pad:pad + w], (e, 1))) and np.all(a[pad:pad + h, pad + w:pad + w + e] == a[pad:pad + h, pad + w - 1:pad + w])

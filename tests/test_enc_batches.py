@@ -21,6 +21,22 @@ def test_a_batch_ends_where_its_halved_offsets_into_the_stacked_originals_reach_
         encode.footprint(c, 897, 2)
 
 
+@pytest.mark.parametrize("threads", [1, 8])
+def test_the_largest_accepted_picture_has_a_footprint_and_its_batch_the_three_limits(threads):
+    """8192x4320, the upper end of what Param::finish takes: the call succeeds, and max_gops is the smallest of the three limits xeve_hip_enc_footprint names -- GOPs x row
+    chains a grid dimension (65535), a stacked picture's rows in 1/16 sample units in 31 bits, the stacked originals below 2^33 samples -- derived here from the sizes:
+    a stacked picture is 4320 + 2 * 144 rows rounded up to 64 = 4608"""
+    vh = (4320 + 2 * 144 + 63) // 64 * 64
+    assert vh == 4608
+    limits = (65535 // threads, (2 ** 31 - 1) // (vh * 32), (2 ** 33 - 1) // (vh * 8192))
+    assert limits == ((65535, 14563, 227) if threads == 1 else (8191, 14563, 227))
+    need, most = encode.footprint(_cfg(8192, 4320, threads), 1, 2)
+    assert most == min(limits) == 227 and need > 2 * 8192 * 4320 * 3  # (more than the two pictures' 16-bit samples)
+    encode.footprint(_cfg(8192, 4320, threads), 227, 2)
+    with pytest.raises(Exception):
+        encode.footprint(_cfg(8192, 4320, threads), 228, 2)
+
+
 def test_the_footprint_is_linear_in_the_gops_and_grows_with_the_frames():
     c = _cfg(3840, 2160)
     b = [encode.footprint(c, n, 2)[0] for n in (1, 2, 3, 896)]

@@ -199,6 +199,30 @@ def test_picture_sizes_modulo_the_ctu_on_the_gpu(name, walk, hip, yuv_dir):
     assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in g["per_gop"]]
 
 
+def _largest_size_params():
+    """both walks (slow and placebo: the fused kernel, the only walk that codes them), all gpu_full: the default suite has no room for a 128-step strip
+    (tests/test_gpu_suite_budget.py); it keeps the leaf tests of the zone (tests/test_hip_me.py, tests/test_hip_inter.py)"""
+    out = []
+    for n in _enc.LARGEST_SIZE_CASES:
+        fused_only = _enc.LARGEST_SIZE_CASES[n][5][1] in ("slow", "placebo")
+        for w in ((1,) if fused_only else (0, 1)):
+            out.append(pytest.param(n, w, id="%s-%s" % (n, WALK_NAME[w]), marks=(pytest.mark.gpu_full,)))
+    return out
+
+
+@pytest.mark.parametrize("name,walk", _largest_size_params())
+def test_the_widest_and_tallest_accepted_pictures_on_the_gpu(name, walk, hip, yuv_dir):
+    """strips of the largest accepted pictures (tests/_enc.py LARGEST_SIZE_CASES) through the device path: 8192 samples wide, where predictors and start vectors that point
+    right wrap in the last CTU column as the reference's s16 frame coordinates do and the searches run at the picture's left end (tests/test_enc_host.py counts on the CPU
+    that these clips get there; the 8128-wide control cannot), and 4320 rows high on one and on eight row chains: every GOP = the unmodified reference's bytes
+    (tests/golden/enc_v1.json), no harness between"""
+    w, h, gops, frames, seed, cli, threads = _enc.LARGEST_SIZE_CASES[name]
+    g = _enc.golden()["batches"][name]
+    with hip.walk_select(walk):
+        outs, _ = _run(hip, _cfg(hip, w, h, cli, threads), [_frames(yuv_dir, name, w, h, gops * frames, seed)], frames)
+    assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in g["per_gop"]]
+
+
 @pytest.mark.parametrize("name", sorted(_e2e.SLOW_CASES))
 def test_preset_slow_single_runs_on_the_gpu(name, hip, yuv_dir):
     """--preset slow on the device (the fused walk: walk_dbk.h estimates the loop filter's share of every candidate's distortion -- rdo_dbk_switch = 1 --, the search

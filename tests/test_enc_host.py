@@ -142,6 +142,27 @@ def test_picture_sizes_modulo_the_ctu_on_the_host_side(name, yuv_dir):
         assert (len(whole), _enc.md5(whole)) == (g["whole"]["bytes"], g["whole"]["md5"])
 
 
+@pytest.mark.parametrize("name", sorted(_enc.LARGEST_SIZE_CASES))
+def test_the_widest_and_tallest_accepted_pictures_on_the_host_side(name, yuv_dir):
+    """strips of the largest accepted pictures (tests/_enc.py LARGEST_SIZE_CASES): 8192 samples wide -- where the reference's s16 quarter-pel frame coordinates wrap in the
+    last CTU column -- and 4320 rows high, every GOP = the unmodified reference's run over it.  Whether a case reaches the zone is counted by the oracle (searches whose
+    frame-coordinate predictor or start vector does not fit an s16): more than none in every 8192-wide case, none in the 8128-wide control, in the tall strips and in
+    8136x16, whose last CU column needs a predictor of 64 samples that this clip (23 samples per frame) cannot supply (the arithmetic: tests/_enc.py)"""
+    import ctypes as C
+
+    w, h, gops, frames, seed, cli, threads = _enc.LARGEST_SIZE_CASES[name]
+    g = _enc.golden()["batches"][name]
+    data = _frames(yuv_dir, name, w, h, gops * frames, seed)
+    H = _enc.harness()
+    H.xo_me_wrapped_searches.restype, H.xo_me_wrapped_searches.argtypes = C.c_long, [C.c_int]
+    H.xo_me_wrapped_searches(1)
+    outs = _enc.encode_cpu(_enc.config(w, h, cli, threads), [data], frames)
+    wrapped = H.xo_me_wrapped_searches(1)
+    print(name, "searches with a wrapped frame coordinate:", wrapped)
+    assert (wrapped > 0) == (name in _enc.LARGEST_SIZE_IN_ZONE) and (w > 8128 or not wrapped), (name, wrapped)
+    assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in g["per_gop"]]
+
+
 @pytest.mark.parametrize("name", sorted(_e2e.SLOW_CASES))
 def test_preset_slow_single_runs(name, yuv_dir):
     """--preset slow: the search's quarter-pel stage, ME range 128 and rdo_dbk_switch = 1 -- every candidate's distortion includes what the loop filter will do to the CU's

@@ -40,7 +40,9 @@ def test_hip_deblock_matches_reference_goldens():
 @pytest.mark.parametrize("w,h,bd,idc,min_cu", [(256, 192, 10, 1, 4), (512, 320, 10, 1, 8), (136, 72, 8, 1, 4), (192, 64, 12, 3, 4), (320, 200, 10, 0, 4),
                                                (1920, 1080, 10, 1, 8),
                                                # pictures below one CTU, one CU row, a partial last CTU column and row (tests/_enc.py PICTURE_SIZE_CASES)
-                                               (8, 8, 10, 1, 4), (24, 40, 10, 1, 4), (64, 8, 10, 1, 8), (200, 8, 10, 1, 4), (88, 80, 10, 1, 8)])
+                                               (8, 8, 10, 1, 4), (24, 40, 10, 1, 4), (64, 8, 10, 1, 8), (200, 8, 10, 1, 4), (88, 80, 10, 1, 8),
+                                               # strips of the widest and of the tallest accepted picture (tests/_enc.py LARGEST_SIZE_CASES)
+                                               (8192, 8, 10, 1, 4), (8, 4320, 10, 1, 4)])
 def test_hip_deblock_vs_oracle(w, h, bd, idc, min_cu):
     O = oracle_df()
     r = np.random.default_rng(w + 3 * h + bd + idc)
@@ -128,7 +130,7 @@ def test_hip_picbuf_expand():
     # a 4:2:0 picture with the reference's padding depths (144 / 72), against the oracle
     O = oracle_df()
     r = np.random.default_rng(7)
-    for w, h, el, ec in ((320, 192, 144, 72), (8, 8, 144, 72), (200, 8, 144, 72)):  # (8x8, 200x8: the padding is far deeper than the picture)
+    for w, h, el, ec in ((320, 192, 144, 72), (8, 8, 144, 72), (200, 8, 144, 72), (8192, 8, 144, 72), (8, 4320, 144, 72)):  # (8x8, 200x8: the padding is far deeper than the picture; the widest and the tallest)
         _expand_vs_oracle(O, r, dev, w, h, el, ec)
 
 

@@ -56,9 +56,9 @@ def run_hip(refs, org, st, P, jobs):
             [ry.cpu().numpy(), ru.cpu().numpy(), rv.cpu().numpy()], nb.cpu().numpy().reshape(-1).view(SBAC_DTYPE))
 
 
-def test_hip_pinter_analyze_cu_matches_reference_goldens():
+def against_goldens(cases):
     n = 0
-    for c in golden():
+    for c in cases:
         res, coef, rec, best = run_hip(c["refs"], c["org"], c["states"], c["P"], c["jobs"])
         got = mask_unobservable(res, c["slice_type"])
         for i in range(len(res)):
@@ -68,7 +68,63 @@ def test_hip_pinter_analyze_cu_matches_reference_goldens():
             assert np.array_equal(rec[k], c["rec"][k]), (n, k)
         assert best.tobytes() == c["best"].tobytes(), n
         n += 1
-    assert n == len(CASES)
+    return n
+
+
+def test_hip_pinter_analyze_cu_matches_reference_goldens():
+    assert against_goldens(golden()) == len(CASES)
+
+
+@pytest.mark.parametrize("k", range(7))
+def test_hip_pinter_analyze_cu_matches_reference_goldens_in_the_last_ctu_of_an_8192_wide_picture(k):
+    """tests/golden/inter_right_edge_v1.npz: CUs of 8 to 64 in the last CTU of an 8192 x 64 picture, B and P slices, neighbour vectors pointing up to 63 samples right, so
+    that the frame coordinates of predictors and start vectors pass an s16 (tests/test_inter_golden.py counts the jobs: 64 of 84)"""
+    from _inter_cases import right_edge_wrapped
+    from _inter_golden import RIGHT_EDGE_CASES
+    from test_inter_golden import RIGHT_EDGE_WRAPPED
+
+    assert len(RIGHT_EDGE_CASES) == 7
+    for c in golden(True, only=k):
+        assert int(right_edge_wrapped(c["jobs"], c["slice_type"]).sum()) == RIGHT_EDGE_WRAPPED[k]  # (on the CPU, before anything goes to the GPU)
+    assert against_goldens(golden(True, only=k)) == 1
+
+
+@pytest.mark.parametrize("slice_type,nref,wrapped", [(0, 2, 79), (1, 1, 75)])
+def test_hip_pinter_analyze_cu_vs_oracle_in_the_last_ctu_of_an_8192_wide_picture(slice_type, nref, wrapped):
+    """the jobs of tests/test_inter_oracle_vs_ref.py's test of the same name (30 per CU size, the oracle held to the reference on them there): cost, motion data, nnz,
+    coefficients, reconstruction and exit coder state"""
+    from _inter_cases import RIGHT_EDGE_H, RIGHT_EDGE_W, make_right_edge_inter_jobs, right_edge_wrapped
+
+    O = oracle_inter()
+    w, h, bd, idc = RIGHT_EDGE_W, RIGHT_EDGE_H, 10, 1
+    r = np.random.default_rng(9300 + slice_type)
+    refs, org = make_inter_picture(r, w, h, bd, nref, idc, slice_type)
+    tab = refpic_table(refs, lambda a, off: int(a.ctypes.data) + 2 * off)
+    st = states(r, 5)
+    org_ptrs = np.array([int(org[0].ctypes.data) + 2 * refs["org_l"], int(org[1].ctypes.data) + 2 * refs["org_c"], int(org[2].ctypes.data) + 2 * refs["org_c"]], np.uint64)
+    sets, n = [], 0
+    for lw in (3, 4, 5, 6):
+        P = make_inter_params(r, lw, w, h, bd, nref, idc, slice_type, refs, 0.0)
+        make_inter_jobs(r, 30, w, h, 1 << lw, len(st), refs, slice_type)  # (the generator's draws as the reference-pinning test makes them)
+        jobs = make_right_edge_inter_jobs(r, 30, 1 << lw, len(st), refs, slice_type)
+        n += int(right_edge_wrapped(jobs, slice_type).sum())
+        sets.append((lw, P, jobs))
+    assert n == wrapped and 3 * n >= 120
+    for lw, P, jobs in sets:
+        cu = 1 << lw
+        res, coef, rec, best = run_hip(refs, org, st, P, jobs)
+        nc = (cu >> refs["ws"]) * (cu >> refs["hs"])
+        for i in range(len(jobs)):
+            er, eb = np.zeros(1, INTER_RESULT_DTYPE), np.zeros(1, SBAC_DTYPE)
+            ec = [np.zeros(cu * cu, np.int16), np.zeros(nc, np.int16), np.zeros(nc, np.int16)]
+            ep = [x.copy() for x in ec]
+            O.xo_pinter_analyze_cu(ptr(org_ptrs), refs["s_l"], refs["s_c"], ptr(tab), refs["s_l"], refs["s_c"], ptr(st), P, ptr(jobs[i:i + 1]), ptr(er), ptr(ec[0]),
+                                   ptr(ec[1]), ptr(ec[2]), ptr(ep[0]), ptr(ep[1]), ptr(ep[2]), ptr(eb))
+            key = (lw, i, jobs[i], res[i], er[0])
+            assert res[i:i + 1].tobytes() == er.tobytes(), key
+            for k in range(3):
+                assert np.array_equal(coef[k][i], ec[k]) and np.array_equal(rec[k][i], ep[k]), (k,) + key
+            assert best[i:i + 1].tobytes() == eb.tobytes(), key
 
 
 @pytest.mark.parametrize("w,h,bd,nref,idc,slice_type,skip_th", [(128, 96, 10, 2, 1, 0, 0.0), (128, 64, 10, 2, 1, 1, 0.0), (96, 64, 8, 1, 1, 0, 0.0),

@@ -318,3 +318,39 @@ def test_epzs_ties_and_clipped_windows_vs_oracle(family, kind):
             for i, c in enumerate(cases):
                 e = run_oracle_epzs(c, with_mot=True)
                 assert (int(cost[i]), int(mv[i, 0]), int(mv[i, 1]), int(mot[i])) == (e[0], e[1], e[2], e[3] if e[3] > 0 else 0), (family, kind, S, bi, v, i, c["mvp"])
+
+
+# ---- the last CTU column of an 8192-wide picture: quarter-pel frame coordinates beyond an s16 -------------------------------------------------------------------------
+@pytest.mark.parametrize("S", [64, 32, 16, 8])
+def test_me_right_edge_matches_reference_goldens_and_oracle(S):
+    """_me_cases' right-edge family at x = 8192 - S: predictors and start vectors whose frame coordinate wraps as the reference's s16 gmvp / mvi do (three jobs of five
+    per launch; each differs from its twin without a wrap -- both asserted on the CPU first, from the reference's recorded results), for bi 0 / 1 / 2 and the ranges of
+    the four presets.  xeve_hip_me_ipel_diamond_jobs takes the wrapped values as its caller hands them down; xeve_hip_me_spel_pattern_jobs wraps cx and mv_x itself (around
+    the true motion, and around the vector the diamond brought back from the picture's left end, which wraps back); xeve_hip_me_epzs_jobs makes gmvp and mvi from the raw
+    mvp -- its own casts -- and runs the raster search and the integer refinement behind a wrapped first search.  Against tests/golden/me_right_edge_v1.npz and, for
+    best_mv_bits, the oracle."""
+    from _me_cases import assert_right_edge_conditions, right_edge_epzs_case, right_edge_spel_case, run_oracle_spel
+    from _me_golden import golden_right_edge_cases
+
+    launches = {}
+    for L, t, c, g in golden_right_edge_cases():
+        if L[0] == S:
+            launches.setdefault(L, []).append((c, g))
+    assert len(launches) == 12
+    assert assert_right_edge_conditions([(L, c, g["dia"], g["twin_dia"], g["epzs"], g["twin_epzs"]) for L, rows in launches.items() for c, g in rows]) == 36
+    for L, rows in launches.items():
+        cases = [c for c, _ in rows]
+        got = gpu_run(cases)
+        for i, (c, g) in enumerate(rows):
+            e, r = run_oracle(c), got[i]
+            assert (int(r["cost"]), int(r["mv"][0]), int(r["mv"][1]), int(r["beststep"])) == g["dia"] and int(r["best_mv_bits"]) == e.best_mv_bits, (L, i, "diamond")
+        for key, scs in (("spel", [right_edge_spel_case(c) for c in cases]), ("spel_at_dia", [right_edge_spel_case(c, g["dia"][1:3]) for c, g in rows])):
+            got = gpu_run_spel(scs)
+            for i, (c, g) in enumerate(rows):
+                e, r = run_oracle_spel(scs[i]), got[i]
+                assert (int(r["cost"]), int(r["mv"][0]), int(r["mv"][1])) == g[key] and int(r["best_mv_bits"]) == e.best_mv_bits, (L, i, key)
+        for key, ipel in (("epzs", False), ("epzs_ipel", True)):
+            cost, mv, mot = gpu_run_epzs([right_edge_epzs_case(c, ipel=ipel) for c in cases])
+            for i, (c, g) in enumerate(rows):
+                e = g[key]
+                assert (int(cost[i]), int(mv[i, 0]), int(mv[i, 1]), int(mot[i])) == (e[0], e[1], e[2], e[3] if e[3] > 0 else 0), (L, i, key, c["mvp"])

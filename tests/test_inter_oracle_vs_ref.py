@@ -12,9 +12,9 @@ from _rdo_cases import states
 pytestmark = pytest.mark.skipif(ref_inter() is None, reason="oracle/_ref not built (no /root/reference here)")
 
 
-def run_both(w, h, bd, nref, idc, slice_type, skip_th, sizes, n, seed, nref1=None, content=None):
+def run_both(w, h, bd, nref, idc, slice_type, skip_th, sizes, n, seed, nref1=None, content=None, right_edge=False):
     """content "flat" / "periodic": every plane of every reference picture and of the original one base (make_degenerate_picture), every other job's predictors integer-pel
-    and the same in both lists"""
+    and the same in both lists; right_edge: the jobs of _inter_cases.make_right_edge_inter_jobs (the last CTU of an 8192 x 64 picture), returns (modes, jobs that wrap)"""
     O, R = oracle_inter(), ref_inter()
     r = np.random.default_rng(seed)
     refs, org = make_inter_picture(r, w, h, bd, nref, idc, slice_type) if content is None else make_degenerate_picture(r, w, h, bd, nref, idc, slice_type, content)
@@ -22,11 +22,16 @@ def run_both(w, h, bd, nref, idc, slice_type, skip_th, sizes, n, seed, nref1=Non
     st = states(r, 5)
     org_ptrs = np.array([int(org[0].ctypes.data) + 2 * refs["org_l"], int(org[1].ctypes.data) + 2 * refs["org_c"], int(org[2].ctypes.data) + 2 * refs["org_c"]],
                         np.uint64)
-    modes = []
+    modes, wrapped = [], 0
     for lw in sizes:
         cu = 1 << lw
         P = make_inter_params(r, lw, w, h, bd, nref, idc, slice_type, refs, skip_th, nref1=nref1)
         jobs = make_inter_jobs(r, n, w, h, cu, len(st), refs, slice_type)
+        if right_edge:
+            from _inter_cases import make_right_edge_inter_jobs, right_edge_wrapped
+
+            jobs = make_right_edge_inter_jobs(r, n, cu, len(st), refs, slice_type)
+            wrapped += int(right_edge_wrapped(jobs, slice_type).sum())
         if content is not None:
             jobs["mvp"][::2, 0] &= ~3
             jobs["mvp"][::2, 1] = jobs["mvp"][::2, 0]
@@ -52,7 +57,19 @@ def run_both(w, h, bd, nref, idc, slice_type, skip_th, sizes, n, seed, nref1=Non
                 assert np.array_equal(pa[k], pb[k]), (k,) + key
             assert ba.tobytes() == bb.tobytes(), key
             modes.append(int(ra["best_idx"][0]))
-    return modes
+    return (modes, wrapped) if right_edge else modes
+
+
+@pytest.mark.parametrize("slice_type,nref,wrapped", [(0, 2, 79), (1, 1, 75)])
+def test_pinter_analyze_cu_in_the_last_ctu_of_an_8192_wide_picture(slice_type, nref, wrapped):
+    """30 CUs of each size 8 to 64 in the last CTU of an 8192 x 64 picture, two of three in its last CU column, neighbour vectors pointing up to 63 samples right: gmvp and
+    mvi of pinter_me_epzs wrap for the jobs counted (none of size 64: 4 * 8128 + 252 = 32 764), the searches run at the picture's left end, check_best_mvp and analyze_bi
+    go on from what they return; merge / skip candidates pass xeve_mv_clip, which computes in int"""
+    from _inter_cases import RIGHT_EDGE_H, RIGHT_EDGE_W
+
+    modes, n = run_both(RIGHT_EDGE_W, RIGHT_EDGE_H, 10, nref, 1, slice_type, 0.0, [3, 4, 5, 6], 30, 9300 + slice_type, right_edge=True)
+    print(n, sorted(set(modes)))
+    assert n == wrapped and 3 * n >= 120 and len(set(modes)) >= 2, (n, modes)
 
 
 @pytest.mark.parametrize("w,h,bd,nref,idc,slice_type", [(128, 96, 10, 2, 1, 0), (128, 64, 10, 2, 1, 1), (96, 64, 8, 1, 1, 0), (64, 64, 10, 2, 0, 0),

@@ -209,3 +209,58 @@ def test_degenerate_fixture_holds_what_the_reference_gives():
         assert [run_ref_epzs(epzs_variant_of(c, v), bd) for v in EPZS_VARIANTS] == ep, (key, n)
         n += 1
     assert n == 24 * len(GOLDEN_SETS)
+
+
+# ---- the last CTU column of an 8192-wide picture: gmvp, mvi, cx, mv_x and every returned vector are s16 in the reference, and there they wrap --------------------------------
+from _me_cases import RE_SIZES  # noqa: E402
+
+
+@pytest.mark.parametrize("S", RE_SIZES)
+def test_searches_match_reference_where_frame_coordinates_pass_an_s16(S):
+    """_me_cases' right-edge family, the 60 jobs of one block size: me_ipel_diamond (bi 0, 1, 2), me_spel_pattern around the true motion and around the diamond's result,
+    pinter_me_epzs with the preset's sub-pel counts (placebo: me_complexity 2, the raster search) and with the integer refinement, and all of it for each job's twin
+    256 samples further left.  (a) three jobs of five per launch wrap; (b) each of them differs from its twin in the reference's results.  The same rows, recorded, are
+    tests/golden/me_right_edge_v1.npz (held to the reference below)."""
+    from _me_cases import (RE_LAUNCHES, assert_right_edge_conditions, right_edge_epzs_case, right_edge_jobs, right_edge_spel_case, run_oracle_epzs, run_oracle_spel)
+
+    entries = []
+    for L in [t for t in RE_LAUNCHES if t[0] == S]:
+        for twin in (False, True):
+            for k, c in enumerate(right_edge_jobs(*L, twin=twin)):
+                cost, mvx, mvy, beststep, mot = dia = run_ref(c)
+                res = run_oracle(c)
+                assert (res.cost, res.mv[0], res.mv[1], res.beststep) == dia[:4], (L, twin, k)
+                if c["bi"] != 1 and res.best_mv_bits > 0:
+                    assert mot == res.best_mv_bits, (L, twin, k)
+                for sc in (right_edge_spel_case(c), right_edge_spel_case(c, (mvx, mvy))):
+                    cost, sx, sy, mot = run_ref_spel(sc)
+                    res = run_oracle_spel(sc)
+                    assert (res.cost, res.mv[0], res.mv[1]) == (cost, sx, sy), (L, twin, k, "spel", sc["mvi"])
+                    if not sc["bi"] and res.best_mv_bits > 0:
+                        assert mot == res.best_mv_bits, (L, twin, k, "spel")
+                ep = None
+                for ipel in (True, False):
+                    ec = right_edge_epzs_case(c, ipel=ipel)
+                    ep = run_ref_epzs(ec)
+                    assert run_oracle_epzs(ec, with_mot=True) == ep, (L, twin, k, "epzs", ipel)
+                if twin:
+                    entries[len(entries) - 5 + k] += (dia[:4], ep)
+                else:
+                    entries.append((L, c, dia[:4], ep))
+    assert_right_edge_conditions([(L, c, dia, tdia, ep, tep) for L, c, dia, ep, tdia, tep in entries])
+
+
+def test_right_edge_fixture_holds_what_the_reference_gives():
+    """tests/golden/me_right_edge_v1.npz (what the CPU suite holds the oracle to and the GPU suite the device code, where there is no reference) against the reference itself"""
+    from _me_cases import RE_JOBS, right_edge_epzs_case, right_edge_jobs, right_edge_spel_case
+    from _me_golden import golden_right_edge_cases
+
+    n = 0
+    for L, t, c, g in golden_right_edge_cases():
+        w = right_edge_jobs(*L, twin=True)[t]
+        assert run_ref(c)[:4] == g["dia"] and run_ref(w)[:4] == g["twin_dia"], (L, t)
+        assert run_ref_spel(right_edge_spel_case(c))[:3] == g["spel"] and run_ref_spel(right_edge_spel_case(c, g["dia"][1:3]))[:3] == g["spel_at_dia"], (L, t)
+        assert run_ref_epzs(right_edge_epzs_case(c)) == g["epzs"] and run_ref_epzs(right_edge_epzs_case(c, ipel=True)) == g["epzs_ipel"], (L, t)
+        assert run_ref_epzs(right_edge_epzs_case(w)) == g["twin_epzs"], (L, t)
+        n += 1
+    assert n == RE_JOBS

@@ -67,7 +67,7 @@ def test_walk_i_pictures_with_count_only_states(case):
 
 
 # ---- P / B slices ------------------------------------------------------------------------------------------------------------------------------------------------
-from _tree_cases import DEGENERATE_INTER_CASES, INTER_CASES, make_inter_case, run_oracle_inter_picture  # noqa: E402
+from _tree_cases import DEGENERATE_INTER_CASES, INTER_CASES, RIGHT_EDGE_INTER_CASES, make_inter_case, make_right_edge_inter_case, run_oracle_inter_picture  # noqa: E402
 
 
 def run_walk_inter_case(c, full=1, threads=1):
@@ -101,8 +101,8 @@ def run_walk_inter_case(c, full=1, threads=1):
     return per_ctu, dict(mod=mod, scu=m["scu"], ipm=m["ipm"], cu_mode=m["cu_mode"], mv=m["mv"], refi=m["refi"])
 
 
-def check_inter(case, threads=1):
-    c = make_inter_case(*case)
+def check_inter(case, threads=1, c=None):
+    c = make_inter_case(*case) if c is None else c
     got, final = run_walk_inter_case(c, threads=threads)
     exp = run_oracle_inter_picture(c)  # updates c["mod"], c["maps"] in place
     for k in range(len(c["order"])):
@@ -122,6 +122,22 @@ def check_inter(case, threads=1):
 def test_walk_p_and_b_pictures_match_oracle(case):
     """(49xx: flat and periodic pictures with identical reference pictures -- walk_inter.h's searches where candidates, reference indices, lists and uni against bi tie)"""
     check_inter(case)
+
+
+@pytest.mark.parametrize("seed,slice_type,wrapped", RIGHT_EDGE_INTER_CASES, ids=["%d-%s" % (c[0], "BP"[c[1]]) for c in RIGHT_EDGE_INTER_CASES])
+def test_walk_matches_oracle_in_the_last_ctus_of_an_8192_wide_picture(seed, slice_type, wrapped):
+    """the last three CTUs of an 8192 x 64 P and B picture, CTU by CTU against the oracle: walk_inter.h's gmvp and start vectors wrap as the reference's s16 frame
+    coordinates do (the oracle counts the searches that get there; it is held to the reference in the zone by tests/test_me_oracle_vs_ref.py and
+    tests/test_inter_oracle_vs_ref.py) -- a difference shows as the CTU, the field and the 4x4 unit, not as a bitstream's md5"""
+    import ctypes as C
+
+    from _libs import oracle
+
+    O = oracle()
+    O.xo_me_wrapped_searches.restype, O.xo_me_wrapped_searches.argtypes = C.c_long, [C.c_int]
+    O.xo_me_wrapped_searches(1)
+    check_inter((seed, slice_type), c=make_right_edge_inter_case(seed, slice_type))
+    assert O.xo_me_wrapped_searches(1) == wrapped
 
 
 def test_walk_periodic_p_picture_with_a_team_of_real_threads():
@@ -250,6 +266,17 @@ def test_walk_decides_every_ctu_of_a_preset_slow_batch(walk_engine, tmp_path_fac
     g = _enc.golden()["batches"][name]
     data, fb = _clip(str(tmp_path_factory.getbasetemp()), name, w, h, gops * frames, seed), w * h * 3 // 2 * frames
     outs = _enc.encode_cpu(_enc.config(w, h, cli, threads), [data[i * fb:(i + 1) * fb] for i in range(gops)], frames)
+    assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in g["per_gop"]]
+
+
+@pytest.mark.parametrize("name", sorted(_enc.LARGEST_SIZE_CASES))
+def test_walk_decides_every_ctu_of_the_widest_and_tallest_accepted_pictures(name, walk_engine, tmp_path_factory):
+    """strips 8192 samples wide and 4320 rows high (tests/_enc.py LARGEST_SIZE_CASES) through the fused walk's host side: walk_inter.h's searches with frame-coordinate
+    predictors and start vectors that wrap as the reference's s16 gmvp / mvi do (tests/test_enc_host.py counts, on the oracle's engine, that the wide cases get there),
+    presets slow and placebo with the quarter-pel stage and the raster search behind a wrapped first search -- against the reference application's bitstreams"""
+    w, h, gops, frames, seed, cli, threads = _enc.LARGEST_SIZE_CASES[name]
+    g = _enc.golden()["batches"][name]
+    outs = _enc.encode_cpu(_enc.config(w, h, cli, threads), [_clip(str(tmp_path_factory.getbasetemp()), name, w, h, gops * frames, seed)], frames)
     assert [(len(o), _enc.md5(o)) for o in outs] == [(p["bytes"], p["md5"]) for p in g["per_gop"]]
 
 

@@ -358,7 +358,9 @@ __global__ void k_spel_make(const xeve_hip_spel_job *__restrict__ jobs, int njob
     const xeve_hip_spel_job jb = jobs[j];
     const int mvx = stage ? res[j].mv[0] : jb.mvi[0], mvy = stage ? res[j].mv[1] : jb.mvi[1];
     const int8_t(*pat)[2] = stage ? c_pat_qpel : c_pat_hpel;
-    const int mx = mvx + (jb.x << 2) + pat[i][0], my = mvy + (jb.y << 2) + pat[i][1]; // quarter pel, picture coordinates (of the stacked batch: jb.y carries the picture)
+    // quarter pel, picture coordinates (of the stacked batch: jb.y carries the picture).  x in 16 bits as the reference's cx and mv_x (xeve_pinter.c:569, 584, 594): the
+    // vector of a search that a wrapped start sent to the picture's left end has wrapped as well, and wraps back here; y never leaves 16 bits (h <= 4320)
+    const int mx = (int16_t)(mvx + (jb.x << 2) + pat[i][0]), my = mvy + (jb.y << 2) + pat[i][1];
     xeve_hip_mc_job m;
     m.gmv_x = mx << 2, m.gmv_y = my << 2; // 1/16 pel, as the reference passes (mv_x << 2), xeve_pinter.c:608
     (void)vh;
@@ -391,7 +393,7 @@ __global__ void k_spel_select(const xeve_hip_spel_job *__restrict__ jobs, int nj
     const int cx = r.mv[0] + (jb.x << 2), cy = r.mv[1] + (jb.y << 2);
     const int8_t(*pat)[2] = stage ? c_pat_qpel : c_pat_hpel;
     for(int i = 0; i < cnt; i++) {
-        const int mx = cx + pat[i][0], my = cy + pat[i][1];
+        const int mx = (int16_t)(cx + pat[i][0]), my = cy + pat[i][1]; // (the position k_spel_make interpolated at)
         int bits = xh_mvd_bits(mx - jb.gmvp[0]) + xh_mvd_bits(my - jb.gmvp[1]) + P.refi_bits;
         if(P.bi) bits += extra ? extra[j] : P.extra_bits;
         const int s = sad[j * cnt + i];

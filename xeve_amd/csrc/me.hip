@@ -340,7 +340,9 @@ __global__ __launch_bounds__(256) void k_me_epzs(const pel *__restrict__ org0, i
             cpl_eval<S, BI>(lorg, ref0, s_ref, nx * ny, [&](int k, int &mx, int &my) { mx = rng[0] + (k % nx) * stp, my = rng[1] + (k / nx) * stp; return true; }, m.gmvp[0],
                             m.gmvp[1], shift, Q, lane, rc, rbits, rx, ry);
             for(int ss = (mult * st0) >> 1; ss > 0; ss >>= 1) {
-                const int cx = rx, cy = ry;
+                // centred on the s16 VECTOR of the best so far, not on its position (:228-234): from the last CTU column of a picture wider than 8128 the vector of
+                // a position at the picture's left end wraps, the centre lies right of every range and the grids find nothing
+                const int cx = ((int16_t)((rx - e.x) << 2) >> 2) + e.x, cy = ry;
                 cpl_eval<S, BI>(lorg, ref0, s_ref, 9,
                                 [&](int k, int &mx, int &my) {
                                     mx = cx + (k % 3 - 1) * ss, my = cy + (k / 3 - 1) * ss;
@@ -359,7 +361,7 @@ __global__ __launch_bounds__(256) void k_me_epzs(const pel *__restrict__ org0, i
     if(EXTRA && ipel_only) { // me_level <= ME_LEV_IPEL: me_ipel_refinement instead of the sub-pel pattern (:835-866, 270-361)
         int16_t rg[4];
         epzs_range(P, e.x + (s.mv[0] >> 2), e.y + (s.mv[1] >> 2), rg);
-        const int ix = clip3(P.min_clip[0], P.max_clip[0], (s.mv[0] + (e.x << 2)) >> 2), iy = clip3(P.min_clip[1], P.max_clip[1], (s.mv[1] + (e.y << 2)) >> 2);
+        const int ix = clip3(P.min_clip[0], P.max_clip[0], (int16_t)(s.mv[0] + (e.x << 2)) >> 2), iy = clip3(P.min_clip[1], P.max_clip[1], (int16_t)(s.mv[1] + (e.y << 2)) >> 2); // (mvi is an s16, :841-842)
         unsigned rc = 0xFFFFFFFFu;
         int rbits = 0, rx = ix, ry = iy;
         cpl_eval<S, BI>(lorg, ref0, s_ref, 9,

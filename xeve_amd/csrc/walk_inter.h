@@ -396,7 +396,7 @@ XW void me_advance(const P &p, MeJob &J, bool first, unsigned cost, int idx, int
         if(idx >= 0 && cost < J.r_cost) {
             int mx, my;
             cand_xy(J, idx, mx, my);
-            J.r_mv[0] = (mx - J.x) << 2, J.r_mv[1] = (my - J.y) << 2, J.r_cost = cost, J.r_bits = bits;
+            J.r_mv[0] = (int16_t)((mx - J.x) << 2), J.r_mv[1] = (int16_t)((my - J.y) << 2), J.r_cost = cost, J.r_bits = bits; // (mv[] is an s16, :212-213: the grids are centred on the WRAPPED vector)
         }
         J.r_pos += J.nc;
         if(J.r_pos < J.r_total) {
@@ -408,7 +408,7 @@ XW void me_advance(const P &p, MeJob &J, bool first, unsigned cost, int idx, int
         return;
     }
     case PH_RASTER_REF: {
-        if(idx >= 0 && cost < J.r_cost) J.r_mv[0] = (J.cx[idx] - J.x) << 2, J.r_mv[1] = (J.cy[idx] - J.y) << 2, J.r_cost = cost, J.r_bits = bits;
+        if(idx >= 0 && cost < J.r_cost) J.r_mv[0] = (int16_t)((J.cx[idx] - J.x) << 2), J.r_mv[1] = (int16_t)((J.cy[idx] - J.y) << 2), J.r_cost = cost, J.r_bits = bits;
         J.r_ss >>= 1;
         if(J.r_ss > 0) raster_ref_round(J);
         else me_raster_done(p, J);
