@@ -894,7 +894,12 @@ int xeve_hip_eco_tile_end_jobs(xeve_hip_sbac *states, int nstates, const xeve_hi
 /* depends on it, as the reference's does).                                                       */
 /* ------------------------------------------------------------------------------------------- */
 typedef struct xeve_hip_enc_config {
-    int32_t w, h;             /* -w / -h: multiples of 8 */
+    int32_t w, h;             /* -w / -h: the INPUT size, as XEVE_PARAM.w / .h are -- multiples of 8, or with reserved[0] bit 5 any positive even numbers whose multiples of 8 above
+                               * them stay within 8192 x 4320 (without the bit such a size is refused, as it was before the bit existed).  The
+                               * picture is CODED at that size, (w + 7) & ~7 by (h + 7) & ~7, as the reference codes it (xeve_enc.c:1574-1583): the frames pushed are
+                               * padded on the device with zeros on the right and below (the application's images are zeroed once and read into), the SPS carries the coded
+                               * size and the cropping window, and the reconstructed pictures come back cropped to w x h.  PSNR / SSE and the --hash digests run over the
+                               * CODED planes, as the application's do. */
     int32_t fps_num, fps_den; /* -z (only the SEI text carries it) */
     int32_t qp;               /* -q */
     int32_t keyint;           /* -I */
@@ -906,7 +911,8 @@ typedef struct xeve_hip_enc_config {
     int32_t ref;              /* --ref (0: the preset's) */
     int32_t reserved[4];      /* [0] bit 0: always run the second writer pass (tests); bit 1: the application's --info 0 (no SEI with the option list); bit 2: measure every picture (xeve_hip_enc_picture_info's
                                * sse / psnr); bit 3: keep the reconstructed pictures (xeve_hip_enc_recon; w * h * 3 bytes per picture of the batch); bit 4: the application's --hash -- every picture is followed by a
-                               * picture-signature SEI with the MD5 of each decoded plane, hashed on the device (xeve_hip_enc_signature; 48 bytes per picture of the batch); bits 8-15: --level-idc (0: 40).  [1]: the application's -d, the input's bit depth -- 0 / 8: one byte per sample;
+                               * picture-signature SEI with the MD5 of each decoded plane, hashed on the device (xeve_hip_enc_signature; 48 bytes per picture of the batch); bit 5: w and h may be any even
+                               * size -- the picture is coded at the next multiples of 8, padded and cropped as the reference does it (see w, h); bits 8-15: --level-idc (0: 40).  [1]: the application's -d, the input's bit depth -- 0 / 8: one byte per sample;
                                * 10: 16-bit little-endian samples (frames pushed are twice as long).  Either way the codec works at 10 bits (--codec-bit-depth).  [2], [3]: --qp-cb-offset / --qp-cr-offset, -12 .. 12
                                * (pinned against the reference LIBRARY: the application lists the options and cannot parse them; 0 with presets slow / placebo). */
 } xeve_hip_enc_config;
@@ -972,6 +978,21 @@ int xeve_hip_enc_recon(xeve_hip_enc *e, int gop, int frame, void *dst, int on_de
  * written.  Two launches (luma, chroma) whatever npics is; npics at most 65535.  Everything is device memory. */
 int xeve_hip_recon_measure(const uint16_t *const rec[3], int s_rec_l, int s_rec_c, int64_t rec_pic_l, int64_t rec_pic_c, const uint16_t *const org[3], int s_org_l, int s_org_c,
                            int64_t org_pic_l, int64_t org_pic_c, int w, int h, int npics, uint16_t *out, int64_t out_pic, uint64_t *sse, void *stream);
+/* The two ends of a picture whose size is even but no multiple of 8 (xeve_amd/csrc/frames.hip), as leaves; the encoder calls them only when the input size differs from the
+ * coded one.  Everything is device memory; both refuse what is outside their contract with XEVE_HIP_ERR_ARG before any launch.
+ * _frames_load: the pushed frames of `npics` pictures -- planar 4:2:0 of src_w x src_h, one byte per sample (depth 8) or 16-bit little-endian (depth 10), no padding,
+ * picture p's frame at frames + p * frame_dist BYTES -- into the w x h original planes org[0..2] at the codec's 10 bits (8-bit samples shifted up by two, 16-bit samples
+ * as they are): strides and picture distances in samples, every sample right of column src_w and below row src_h set to 0.  src_w, src_h even, at most w, h; w, h
+ * multiples of 8 within 8 .. 8192 x 8 .. 4320; org as xeve_hip_recon_measure's planes (luma 16-byte, chroma 8-byte aligned rows).  Exactly the w x h (w / 2 x h / 2)
+ * window of each output plane is written.  Two launches (luma, both chroma planes) whatever npics is; npics at most 65535.
+ * _recon_crop: the cw x ch window at the top left of `npics` stacked pictures (planes rec[0..2], strides and picture distances as xeve_hip_recon_measure takes them) into
+ * `out` -- per picture Y, then U, then V, rows of cw (cw / 2) samples without padding, pictures out_pic samples apart: the application's -r layout.  cw, ch even; `out`
+ * needs 2-byte alignment only and out_pic any value from cw * ch * 3 / 2.  The chunks of 8 (4) samples a row's window touches are read whole, so the strides hold cw (cw / 2)
+ * rounded up to 8 (4); nothing outside the described rows of `out` is written. */
+int xeve_hip_frames_load(const uint8_t *frames, int64_t frame_dist, int depth, int src_w, int src_h, int w, int h, uint16_t *const org[3], int s_org_l, int s_org_c,
+                         int64_t org_pic_l, int64_t org_pic_c, int npics, void *stream);
+int xeve_hip_recon_crop(const uint16_t *const rec[3], int s_rec_l, int s_rec_c, int64_t rec_pic_l, int64_t rec_pic_c, int cw, int ch, int npics, uint16_t *out, int64_t out_pic,
+                        void *stream);
 
 /* The application's --hash (reserved[0] bit 4): behind every picture's slice NAL unit the bitstream carries a picture-signature SEI NAL unit at the picture's temporal id
  * (xeve_pic_finish, src_base/xeve_enc.c:1255-1271; xeve_eco_signature, xeve_eco.c:300-322) -- payload type 0x10, the size byte 0x10, then the MD5 of the decoded Y, U and V

@@ -27,7 +27,7 @@ enum { PAD_L = 144, PAD_C = 72, BIT_DEPTH = 10, LOG2_CTU = 6, CTU = 64, MAX_ACTI
 
 // ---- encoder parameters: xeve_param_init (xeve_enc.c:2290-2324) + xeve_param_apply_ppt_baseline (:2431-2531) + xeve_set_init_param (:2210-2288) -----------------------
 struct Param {
-    int w = 0, h = 0, fps_num = 30, fps_den = 1, qp = 32, keyint = 0, bframes = 15, closed_gop = 0, threads = 1, inter_slice_type = 0, ref = 0;
+    int w = 0, h = 0, src_w = 0, src_h = 0, fps_num = 30, fps_den = 1, qp = 32, keyint = 0, bframes = 15, closed_gop = 0, threads = 1, inter_slice_type = 0, ref = 0;
     int preset = 1; // 0 fast, 1 medium, 2 slow, 3 placebo
     int qp_cb_offset = 0, qp_cr_offset = 0; // --qp-cb-offset / --qp-cr-offset (sh->qp_u_offset / qp_v_offset, xeve_enc.c:1509-1510)
     int level_idc = 40, sei_info = 1; // --level-idc (sps->level_idc = 3 x, xeve_enc.c:1402) and --info (the SEI that lists the options, :1989)
@@ -45,8 +45,17 @@ struct Param {
         qp_cb_offset = c.reserved[2], qp_cr_offset = c.reserved[3];
         level_idc = ((c.reserved[0] >> 8) & 0xFF) ? ((c.reserved[0] >> 8) & 0xFF) : 40, sei_info = (c.reserved[0] & 2) ? 0 : 1, hash = (c.reserved[0] & 16) ? 1 : 0;
         auto bad = [&](const char *m) { error = m; return false; };
-        if(w <= 0 || h <= 0 || (w & 7) || (h & 7)) return bad("picture size must be a positive multiple of 8 in both directions");
-        if(w > 8192 || h > 4320) return bad("picture larger than 8192x4320");
+        // c.w / c.h are the INPUT size, as XEVE_PARAM.w / .h are: the reference refuses odd sizes only (xeve.c:412-422) and codes ALIGN8 of both (xeve_enc.c:1574-1583).
+        // From here on w, h are the CODED size; src_w, src_h keep the input's (the cropping window of the SPS, the option SEI's text, the motion search's clip).
+        // The caller says so with reserved[0] bit 5 (xeve_amd.encode.config(..., crop=True)): without it a size that is no multiple of 8 stays refused as it always was --
+        // a caller that never heard of cropping is not handed a stream whose coded size differs from what it pushed and PSNRs that count padding.
+        if(w <= 0 || h <= 0) return bad("picture size must be positive in both directions");
+        if(!(c.reserved[0] & 32) && ((w & 7) || (h & 7)))
+            return bad("picture size must be a positive multiple of 8 in both directions (reserved[0] bit 5 accepts any even size: coded at the next multiples of 8, padded and cropped)");
+        if(w & 1) return bad("picture width must be even (4:2:0)");
+        if(h & 1) return bad("picture height must be even (4:2:0)");
+        src_w = w, src_h = h, w = (int)(((long)w + 7) & ~7L), h = (int)(((long)h + 7) & ~7L);
+        if(w > 8192 || h > 4320) return bad("picture larger than 8192x4320 (the coded size: width and height rounded up to multiples of 8)");
         if(qp < 0 || qp > 51 || keyint < 0 || threads < 1 || threads > 8 || fps_num <= 0 || fps_den <= 0) return bad("qp / keyint / threads / fps out of range");
         if(!(bframes == 0 || bframes == 1 || bframes == 3 || bframes == 7 || bframes == 15)) return bad("bframes must be 0, 1, 3, 7 or 15");
         if(bframes && !closed_gop && keyint % (bframes + 1) != 0) return bad("an open GOP needs keyint to be a multiple of bframes + 1");
@@ -82,7 +91,11 @@ struct Param {
         lookahead = std::min(std::max(0, 17), MAX_INBUF >> 1);
         return true;
     }
-    long frame_bytes() const { return (long)w * h * 3 / 2 * (input_depth > 8 ? 2 : 1); } // one planar 4:2:0 input frame
+    long frame_bytes() const { return (long)w * h * 3 / 2 * (input_depth > 8 ? 2 : 1); } // one planar 4:2:0 frame of the CODED size
+    long input_frame_bytes() const { return (long)src_w * src_h * 3 / 2 * (input_depth > 8 ? 2 : 1); } // one planar 4:2:0 frame as the user holds it
+    bool cropped() const { return src_w != w || src_h != h; }
+    int  crop_right() const { return (w - src_w + 1) >> 1; }   // xeve_set_sps (xeve_enc.c:1432-1437): in chroma samples
+    int  crop_bottom() const { return (h - src_h + 1) >> 1; }
     int max_num_ref_pics() const { return bframes > 0 ? me_ref_num : ref_pic_gap_length; } // xeve_set_sps (xeve_enc.c:1413-1419)
 };
 
@@ -388,7 +401,10 @@ inline std::vector<uint8_t> make_sps(const Param &P) // xeve_set_sps + xeve_eco_
     const int log2_sub_gop = (int)(std::log2((double)P.gop_size) + .5);
     bs.ue((uint32_t)log2_sub_gop);
     if(log2_sub_gop == 0) bs.ue((uint32_t)(int)(std::log2((double)P.ref_pic_gap_length) + .5));
-    bs.ue((uint32_t)P.max_num_ref_pics()), bs.put(0, 1) /* cropping */, bs.put(0, 1) /* chroma_qp_table_present_flag */, bs.put(0, 1) /* vui */;
+    bs.ue((uint32_t)P.max_num_ref_pics());
+    bs.put(P.cropped() ? 1 : 0, 1); // picture_cropping_flag (xeve_eco.c:176-181): left, right, top, bottom
+    if(P.cropped()) bs.ue(0), bs.ue((uint32_t)P.crop_right()), bs.ue(0), bs.ue((uint32_t)P.crop_bottom());
+    bs.put(0, 1) /* chroma_qp_table_present_flag */, bs.put(0, 1) /* vui */;
     bs.align();
     nal_close(bs.b);
     return bs.b;
@@ -418,7 +434,7 @@ inline std::string sei_text(const Param &P) // xeve_eco_emitsei's banner + xeve_
     const int cs = (BIT_DEPTH << 8) | 11; // XEVE_CS_SET(XEVE_CF_YCBCR420, 10, 0): the application hands the codec 10-bit pictures
     std::string s = " xeve - MPEG-5 EVC codec - ESSENTIAL VIDEO CODING https://github.com/mpeg5/xeve - options: ";
     struct KV { const char *k; int v; };
-    s += fmt("profile=%d threads=%d input-res=%dx%d fps=%.3f keyint=%d color-space=%d rc-type=CQP", 0, P.threads, P.w, P.h, (float)P.fps_num / P.fps_den, P.keyint, cs);
+    s += fmt("profile=%d threads=%d input-res=%dx%d fps=%.3f keyint=%d color-space=%d rc-type=CQP", 0, P.threads, P.src_w - P.crop_right(), P.src_h - P.crop_bottom(), (float)P.fps_num / P.fps_den, P.keyint, cs);
     const KV a[] = {{"qp", P.qp}, {"qp_cb_offset", P.qp_cb_offset}, {"qp_cr_offset", P.qp_cr_offset}, {"info", P.sei_info}, {"hash", P.hash}, {"bframes", P.bframes}, {"aq-mode", 0}, {"lookahead", P.lookahead},
                     {"closed-gop", P.closed_gop}, {"disable-hgop", 0}, {"ref_pic_gap_length", P.ref_pic_gap_length}, {"codec-bit-depth", BIT_DEPTH}, {"level-idc", P.level_idc},
                     {"cu-tree", 0}, {"constrained-ip", 0}, {"use-deblock", 1}, {"inter-slice-type", P.inter_slice_type}, {"rdo-deblk-switch", P.rdo_dbk},
@@ -574,7 +590,7 @@ inline void fill_inter_params(xeve_hip_tree_inter &I, const Param &P, int slice_
     p.rdo.dist_chroma_weight[0] = n.dcw[0], p.rdo.dist_chroma_weight[1] = n.dcw[1];
     const int range = P.bframes == 0 ? 64 : P.me_range; // SEARCH_RANGE_IPEL_LD
     p.me.me.lambda_mv = n.lambda_mv, p.me.me.faststep = 3, p.me.me.max_search_range = range;
-    p.me.me.min_clip[0] = p.me.me.min_clip[1] = -128 + 1, p.me.me.max_clip[0] = P.w - 1, p.me.me.max_clip[1] = P.h - 1; // xeve_pinter_create (xeve_pinter.c:2124-2127)
+    p.me.me.min_clip[0] = p.me.me.min_clip[1] = -128 + 1, p.me.me.max_clip[0] = P.src_w - 1, p.me.me.max_clip[1] = P.src_h - 1; // xeve_pinter_create (xeve_pinter.c:2124-2127): the INPUT size
     p.me.hpel_cnt = P.me_sub > 1 ? P.me_sub_pos : 0, p.me.qpel_cnt = P.me_sub > 2 ? P.me_sub_pos : 0;
     p.me.me.reserved = P.me_algo > 1 ? 1 : 0;
     for(int l = 0; l < 2; l++)

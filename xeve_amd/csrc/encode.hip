@@ -252,7 +252,7 @@ struct xeve_hip_enc {
     std::vector<std::vector<uint8_t>> bitstreams;
     std::unique_ptr<BatchEncoder<xeve_hip_enc>> loop; // the frame loop of the run in progress (xeve_hip_enc_begin .. the advance that returns 0)
     // What the reference returns with every picture beside its bytes (reserved[0] bit 2: the squared differences against the original; bit 3: the reconstructed picture),
-    // taken at the picture's end from the store and from `org` -- both are overwritten soon afterwards.  kept: [display frame][GOP][w * h * 3 / 2] samples, sums:
+    // taken at the picture's end from the store and from `org` -- both are overwritten soon afterwards.  kept: [display frame][GOP][src_w * src_h * 3 / 2] samples (the cropped window), sums:
     // [display frame][GOP][3].  A picture is SERVED once its access unit is in the bitstream: the frame loop's collect() precedes exactly that append.
     DevBuf kept, sums;
     std::vector<PicPlan>  pics;        // the run's pictures in coding order
@@ -284,7 +284,7 @@ struct xeve_hip_enc {
     {
         for(int c = 0; c < 3; c++) memcpy(out + 16 * c, h_digs + (((size_t)frame * 3 + c) * G + g) * 16, 16);
     }
-    size_t pic_samples() const { return (size_t)P.w * P.h * 3 / 2; }
+    size_t pic_samples() const { return (size_t)P.src_w * P.src_h * 3 / 2; } // a kept picture: the CROPPED window (the input size; the coded one where nothing is cropped)
     bool begin_run()
     {
         n_served = 0, digs_frame = -1;
@@ -315,7 +315,7 @@ struct xeve_hip_enc {
         w_scu = P.w >> 2, h_scu = P.h >> 2, w_lcu = (P.w + CTU - 1) / CTU, h_lcu = (P.h + CTU - 1) / CTU, f_lcu = w_lcu * h_lcu, T = std::min(P.threads, h_lcu);
         vh = (P.h + 2 * PAD_L + 63) & ~63, s_l = P.w + 2 * PAD_L, s_c = P.w / 2 + 2 * PAD_C;
         org_l = (long)vh * P.w, org_c = (long)(vh / 2) * (P.w / 2), pic_l = (long)vh * s_l, pic_c = (long)(vh / 2) * s_c, map_pic = (long)(vh / 4) * w_scu;
-        frame_bytes = P.frame_bytes();
+        frame_bytes = P.input_frame_bytes(); // (the frames stay as they are pushed: rows of src_w samples; begin_picture pads them into `org`)
         if((double)G * org_l >= 8589934592.0) return fail("too many GOPs for one batch at this picture size: the stacked originals must stay below 2^33 samples (xh_common.h: halved 32-bit offsets)");
         if((long)G * T > 65535) return fail("too many GOPs for one batch: GOPs x row chains is a grid dimension (at most 65535)");
         if((double)G * vh * 32 >= 2147483648.0) return fail("too many GOPs for one batch at this picture size: the tall picture's rows in 1/16 sample units must fit 31 bits");
@@ -473,7 +473,14 @@ struct xeve_hip_enc {
         if(!error.empty()) return;
         const long n = (long)P.w * P.h;
         const dim3 lg((unsigned)((n + 255) / 256), G);
-        if(P.input_depth > 8)
+        if(P.cropped()) { // an even size that is no multiple of 8: the frames' rows are src_w samples long, the coded planes get zeros right of them and below (frames.hip)
+            uint16_t *const o[3] = {org[0].as<uint16_t>(), org[1].as<uint16_t>(), org[2].as<uint16_t>()};
+            if(!rc_ok(xeve_hip_frames_load(frames.as<uint8_t>() + (size_t)pos_of_frame[S.frame] * G * frame_bytes, frame_bytes, P.input_depth, P.src_w, P.src_h, P.w, P.h, o, P.w,
+                                           P.w / 2, org_l, org_c, G, st),
+                      "xeve_hip_frames_load"))
+                return;
+        }
+        else if(P.input_depth > 8)
             k_enc_load<uint16_t, 0><<<lg, 256, 0, st>>>(frames.as<uint8_t>(), frame_bytes, (long)pos_of_frame[S.frame] * G * frame_bytes, org[0].as<pel>(), org[1].as<pel>(),
                                                         org[2].as<pel>(), P.w, P.h, org_l, org_c);
         else
@@ -550,9 +557,15 @@ struct xeve_hip_enc {
             const uint16_t *r[3], *o[3];
             for(int c = 0; c < 3; c++) r[c] = reinterpret_cast<const uint16_t *>(slot_plane(S.cur_slot, c)), o[c] = org[c].as<uint16_t>();
             const size_t at = (size_t)S.frame * G;
-            if(!rc_ok(xeve_hip_recon_measure(r, s_l, s_c, pic_l, pic_c, o, P.w, P.w / 2, org_l, org_c, P.w, P.h, G, keeps_recon() ? kept.as<uint16_t>() + at * pic_samples() : nullptr,
+            // (a cropped size: the sums run over the CODED planes against the zero-padded original, as the application's cal_psnr does; the kept picture is the window)
+            const bool copies = keeps_recon() && !P.cropped();
+            if((measures() || copies) &&
+               !rc_ok(xeve_hip_recon_measure(r, s_l, s_c, pic_l, pic_c, o, P.w, P.w / 2, org_l, org_c, P.w, P.h, G, copies ? kept.as<uint16_t>() + at * pic_samples() : nullptr,
                                              (int64_t)pic_samples(), measures() ? sums.as<uint64_t>() + at * 3 : nullptr, st),
                       "xeve_hip_recon_measure"))
+                return;
+            if(keeps_recon() && P.cropped() &&
+               !rc_ok(xeve_hip_recon_crop(r, s_l, s_c, pic_l, pic_c, P.src_w, P.src_h, G, kept.as<uint16_t>() + at * pic_samples(), (int64_t)pic_samples(), st), "xeve_hip_recon_crop"))
                 return;
         }
         if(hashes()) { // the same place: the 3 * G planes of the store in ONE launch, and their 48 * G bytes to the host on the stream that made them

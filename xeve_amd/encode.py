@@ -23,17 +23,19 @@ def stats_line(p):
 
 
 def config(w, h, qp=32, keyint=0, bframes=15, closed_gop=False, preset="medium", threads=1, fps=(30, 1), ref=0, always_second_pass=False, input_depth=8, level_idc=40, sei_info=True,
-           inter_slice_type=0, qp_cb_offset=0, qp_cr_offset=0, measure=False, keep_recon=False, hash=False):
+           inter_slice_type=0, qp_cb_offset=0, qp_cr_offset=0, measure=False, keep_recon=False, hash=False, crop=False):
     """the options of the reference application (xeve_app: -w -h -q -I -b --closed-gop --preset -m -z --ref -d; --inter-slice-type 0 B / 1 P, --qp-cb-offset,
     --qp-cr-offset as the reference LIBRARY takes them) as the library's configuration record.  measure: per-picture SSE / PSNR (BatchEncoder.pictures);
     keep_recon: the reconstructed pictures stay on the device (BatchEncoder.recon; w * h * 3 bytes per picture of the batch) -- neither changes the bitstream.
     hash: the application's --hash -- a 56-byte picture-signature SEI with the MD5 of each decoded plane behind every picture (BatchEncoder.signatures), hash=1 in the
-    option SEI; the digests are made on the device"""
+    option SEI; the digests are made on the device.  crop: w and h may be any even size (960x540, 1366x768) -- the picture is coded at the next multiples of 8 with zeros
+    right of the input and below it and a cropping window in the SPS, as the reference codes it; frames are pushed and recon() is handed out at w x h, PSNR and the hash
+    digests run over the coded planes as the application's do.  Without it a size that is no multiple of 8 is refused"""
     c = _lib.EncConfig()
     c.w, c.h, c.fps_num, c.fps_den, c.qp, c.keyint, c.bframes, c.closed_gop = w, h, fps[0], fps[1], qp, keyint, bframes, int(bool(closed_gop))
     c.preset, c.threads, c.inter_slice_type, c.ref = PRESETS[preset] if isinstance(preset, str) else int(preset), threads, int(inter_slice_type), ref
     c.reserved[2], c.reserved[3] = int(qp_cb_offset), int(qp_cr_offset)
-    c.reserved[0] = (1 if always_second_pass else 0) | (0 if sei_info else 2) | (4 if measure else 0) | (8 if keep_recon else 0) | (16 if hash else 0) | ((int(level_idc) & 0xFF) << 8)  # (--info 0, --level-idc)
+    c.reserved[0] = (1 if always_second_pass else 0) | (0 if sei_info else 2) | (4 if measure else 0) | (8 if keep_recon else 0) | (16 if hash else 0) | (32 if crop else 0) | ((int(level_idc) & 0xFF) << 8)  # (--info 0, --level-idc)
     c.reserved[1] = int(input_depth)
     return c
 

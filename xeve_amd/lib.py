@@ -285,6 +285,9 @@ FUNCTIONS = {
     "xeve_hip_enc_picture_info": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "xeve_hip_enc_recon": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),
     "xeve_hip_recon_measure": (c_int, [c_void_p, c_int, c_int, c_i64, c_i64, c_void_p, c_int, c_int, c_i64, c_i64, c_int, c_int, c_int, c_void_p, c_i64, c_void_p, c_void_p]),
+    # even picture sizes that are no multiple of 8: the padded load of the pushed frames, the cropped copy of the reconstructed pictures
+    "xeve_hip_frames_load": (c_int, [c_void_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_i64, c_i64, c_int, c_void_p]),
+    "xeve_hip_recon_crop": (c_int, [c_void_p, c_int, c_int, c_i64, c_i64, c_int, c_int, c_int, c_void_p, c_i64, c_void_p]),
     # the application's --hash: decoded-picture MD5s made on the device, the picture-signature SEI
     "xeve_hip_md5_planes": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "xeve_hip_enc_signature": (c_int, [c_void_p, c_int, c_int, c_void_p]),
