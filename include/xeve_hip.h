@@ -994,6 +994,57 @@ int xeve_hip_frames_load(const uint8_t *frames, int64_t frame_dist, int depth, i
 int xeve_hip_recon_crop(const uint16_t *const rec[3], int s_rec_l, int s_rec_c, int64_t rec_pic_l, int64_t rec_pic_c, int cw, int ch, int npics, uint16_t *out, int64_t out_pic,
                         void *stream);
 
+/* RGB TENSORS IN AND OUT (xeve_amd/csrc/color.hip, color_core.h).  The frames a GPU produces are RGB; the codec takes and returns planar 4:2:0 Y'CbCr.  The two leaves
+ * convert between them on the device, the two encoder entry points below put them at the encoder's ends.  The reference has no counterpart (its application reads and
+ * writes Y'CbCr files): the arithmetic is this library's own, ALL INTEGER, and fully stated here, so a result is the same bits on every device and on the host.
+ * THE STREAM CARRIES NO COLOUR DESCRIPTION (no VUI), as the reference's default streams carry none: the container or the consumer has to be told which matrix, range and
+ * siting were used.
+ * A component becomes c16 = 0 .. 65535: uint8 v -> v * 257; float16 / bfloat16 / float32 -> widened to float32, NaN -> 0, clamped to [0, 1], floor(x * 65535 + 0.5) with the
+ * product and the sum each rounded to float32 (no fused multiply-add).
+ * Coefficients, S = 24: Kr, Kb are the exact decimals (bt601 0.299 / 0.114, bt709 0.2126 / 0.0722, bt2020nc 0.2627 / 0.0593), Kg = 1 - Kr - Kb; limited range
+ * sY = 219 * 2^(d-8), sC = 224 * 2^(d-8), oY = 16 * 2^(d-8); full range sY = sC = 2^d - 1, oY = 0; oC = 2^(d-1); rnd = round half away from zero of the exact rational;
+ * a = sY * 2^S / 65535, c = sC * 2^S / 65535.  Luma row: mYR = rnd(a Kr), mYB = rnd(a Kb), mYG = rnd(a) - mYR - mYB.  Cb row: mB = rnd(c / 2), mR = rnd(-c Kr / (2 (1 - Kb))),
+ * mG = -mB - mR.  Cr row: mR = rnd(c / 2), mB = rnd(-c Kb / (2 (1 - Kr))), mG = -mR - mB (chroma rows sum to 0: greys give exactly oC).
+ * Forward (int64, >> is the arithmetic shift): Y = clamp((mY . c16 + (oY << S) + (1 << (S-1))) >> S, 0, 2^d - 1) per pixel; a chroma sample from the SUM of the c16 triples
+ * over its taps -- siting 1 (centre): luma columns 2i, 2i+1, rows 2j, 2j+1, weights 1, L = 2; siting 0 (left; chroma_sample_loc_type 0, what decoders assume when nothing is
+ * signalled): columns 2i-1, 2i, 2i+1 with weights 1 2 1 (columns clamped to the picture), rows 2j, 2j+1, L = 3 -- C = clamp((m . sum + (oC << (S+L)) + (1 << (S+L-1))) >> (S+L),
+ * 0, 2^d - 1).
+ * Inverse (d = 10 always: the codec's reconstruction): iY = rnd(65535 * 2^S / sY); with ic = 65535 * 2^S / sC: rCr = rnd(2 (1 - Kr) ic), bCb = rnd(2 (1 - Kb) ic),
+ * gCb = rnd(-2 Kb (1 - Kb) / Kg ic), gCr = rnd(-2 Kr (1 - Kr) / Kg ic).  Chroma at a luma pixel is bilinear, a sum of weight 16: vertically rows cy = y >> 1 and cy + 1 (odd y) /
+ * cy - 1 (even y), clamped, weights 3 : 1; horizontally the same rule for siting centre, for siting left even x takes column x >> 1 alone (weight 4), odd x columns x >> 1 and
+ * (x >> 1) + 1, clamped, weights 2 : 2.  R16 = clamp((16 iY (Y - oY) + rCr (sumCr - 16 oC) + (1 << (S+3))) >> (S+4), 0, 65535), G with gCb and gCr, B with bCb.  Output: uint8
+ * (R16 + 128) / 257; float32 (float)R16 / 65535.0f; float16 / bfloat16 that float32 rounded to nearest-even.
+ * yuv is what xeve_hip_enc_push takes and xeve_hip_enc_recon hands out: planar Y, U, V, rows of w (w / 2) samples without padding; a sample is one byte at depth 8, 16-bit
+ * little-endian at depth 10 (sample-aligned; the inverse reads 10-bit samples only and refuses another depth).  Picture p's frame lies p * yuv_pic_bytes (_samples) behind
+ * the first.  The tensor side is ANY VIEW: element (picture p, row y, column x, component c) at p * stride_pic + y * stride_y + x * stride_x + c * stride_c ELEMENTS from rgb;
+ * an input's strides may be 0 (an expanded axis), an output's are at least 1 and its elements are the caller's to keep distinct.  w, h even within 2 .. 8192 x 2 .. 4320, npics
+ * at most 65535, everything device memory; anything else is refused with XEVE_HIP_ERR_ARG before any launch.  Nothing outside the described samples is read or written.
+ * One launch whatever npics is.
+ * xeve_hip_color_matrix: the coefficients -- fwd = the rows Y, Cb, Cr over R, G, B at color->depth, fwd_off = { oY, oC } at color->depth, inv = { iY, rCr, gCb, gCr, bCb }
+ * (always d = 10).  Host only, no device call, usable before xeve_hip_init. */
+typedef struct xeve_hip_color {
+    int32_t matrix;     /* 0 bt601, 1 bt709, 2 bt2020nc */
+    int32_t full_range; /* 0 limited, 1 full */
+    int32_t siting;     /* 0 left, 1 centre */
+    int32_t depth;      /* of the Y'CbCr side: 8 | 10 */
+} xeve_hip_color;
+typedef struct xeve_hip_rgb_desc {
+    int32_t dtype;      /* 0 uint8, 1 float16, 2 bfloat16, 3 float32 */
+    int32_t reserved;
+    int64_t stride_x, stride_y, stride_c, stride_pic; /* in ELEMENTS */
+} xeve_hip_rgb_desc;
+int xeve_hip_rgb_to_yuv420(const void *rgb, const xeve_hip_rgb_desc *desc, const xeve_hip_color *color, int w, int h, int npics, void *yuv, int64_t yuv_pic_bytes, void *stream);
+int xeve_hip_yuv420_to_rgb(const uint16_t *yuv, int64_t yuv_pic_samples, const xeve_hip_color *color, int w, int h, int npics, void *rgb, const xeve_hip_rgb_desc *desc,
+                           void *stream);
+int xeve_hip_color_matrix(const xeve_hip_color *color, int64_t fwd[9], int64_t fwd_off[2], int64_t inv[5]);
+/* The encoder's ends.  _push_rgb is xeve_hip_enc_push for an RGB picture of the INPUT size (cfg.w x cfg.h, also with reserved[0] bit 5): converted straight into the frame's
+ * place in HBM at the run's input depth -- color->depth must equal it (8, or 10 with reserved[1] = 10), or the call is refused -- on the encoder's stream, complete when the call
+ * returns; it counts as a push.  rgb is device memory of the encoder's GPU, COMPLETE when the call is made (host memory or another GPU's is refused).
+ * _recon_rgb is xeve_hip_enc_recon as RGB: it needs reserved[0] bit 3, has the same validity rules and refusals, reads the kept picture (color->depth is 10) and is complete
+ * when it returns.  With neither called nothing is allocated or launched: footprint, max_gops and every bitstream are what they are without them. */
+int xeve_hip_enc_push_rgb(xeve_hip_enc *e, int gop, int frame, const void *rgb, const xeve_hip_rgb_desc *desc, const xeve_hip_color *color);
+int xeve_hip_enc_recon_rgb(xeve_hip_enc *e, int gop, int frame, void *rgb, const xeve_hip_rgb_desc *desc, const xeve_hip_color *color);
+
 /* The application's --hash (reserved[0] bit 4): behind every picture's slice NAL unit the bitstream carries a picture-signature SEI NAL unit at the picture's temporal id
  * (xeve_pic_finish, src_base/xeve_enc.c:1255-1271; xeve_eco_signature, xeve_eco.c:300-322) -- payload type 0x10, the size byte 0x10, then the MD5 of the decoded Y, U and V
  * plane (the size byte says 16 although 48 bytes follow: reproduced as it is).  The unit is always XEVE_HIP_SIGNATURE_SEI_BYTES long, and the SEI with the option list in

@@ -831,6 +831,51 @@ extern "C" int xeve_hip_enc_recon(xeve_hip_enc *e, int gop, int frame, void *dst
     XH_HIP(hipStreamSynchronize(e->st));
     return XEVE_HIP_OK;
 }
+// RGB at the encoder's two ends (color.hip): the conversions run on the encoder's stream, straight into the frame's place / out of the kept picture
+static bool on_encoders_gpu(const xeve_hip_enc *e, const void *p)
+{
+    hipPointerAttribute_t a;
+    if(hipPointerGetAttributes(&a, p) != hipSuccess || a.type == hipMemoryTypeHost || a.type != hipMemoryTypeDevice || a.device != e->device) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return true;
+}
+extern "C" int xeve_hip_enc_push_rgb(xeve_hip_enc *e, int gop, int frame, const void *rgb, const xeve_hip_rgb_desc *desc, const xeve_hip_color *color)
+{
+    XH_ENTER();
+    XH_REQUIRE(e && rgb && desc && color && gop >= 0 && gop < e->G && frame >= 0 && frame < e->F);
+    if(color->depth != (e->P.input_depth > 8 ? 10 : 8)) {
+        xh_set_error("xeve_hip_enc_push_rgb: color.depth (%d) is not the run's input depth (%d)", color->depth, e->P.input_depth > 8 ? 10 : 8);
+        return XEVE_HIP_ERR_ARG;
+    }
+    if(!on_encoders_gpu(e, rgb)) {
+        xh_set_error("xeve_hip_enc_push_rgb: rgb is not device memory of the encoder's GPU (%d)", e->device);
+        return XEVE_HIP_ERR_ARG;
+    }
+    const int rc = xeve_hip_rgb_to_yuv420(rgb, desc, color, e->P.src_w, e->P.src_h, 1, e->frames.as<uint8_t>() + ((size_t)e->pos_of_frame[frame] * e->G + gop) * e->frame_bytes,
+                                          (int64_t)e->frame_bytes, e->st);
+    if(rc != XEVE_HIP_OK) return rc;
+    XH_HIP(hipStreamSynchronize(e->st));
+    e->pushed++;
+    return XEVE_HIP_OK;
+}
+extern "C" int xeve_hip_enc_recon_rgb(xeve_hip_enc *e, int gop, int frame, void *rgb, const xeve_hip_rgb_desc *desc, const xeve_hip_color *color)
+{
+    XH_ENTER();
+    XH_REQUIRE(e && rgb && desc && color);
+    if(!e->keeps_recon()) { xh_set_error("xeve_hip_enc_recon_rgb: the run was created without reserved[0] bit 3 (keep the reconstructed pictures)"); return XEVE_HIP_ERR_ARG; }
+    if(served_position(e, "xeve_hip_enc_recon_rgb", gop, frame) < 0) return XEVE_HIP_ERR_ARG;
+    if(!on_encoders_gpu(e, rgb)) {
+        xh_set_error("xeve_hip_enc_recon_rgb: rgb is not device memory of the encoder's GPU (%d)", e->device);
+        return XEVE_HIP_ERR_ARG;
+    }
+    const int rc = xeve_hip_yuv420_to_rgb(e->kept.as<uint16_t>() + ((size_t)frame * e->G + gop) * e->pic_samples(), (int64_t)e->pic_samples(), color, e->P.src_w, e->P.src_h, 1, rgb, desc,
+                                          e->st);
+    if(rc != XEVE_HIP_OK) return rc;
+    XH_HIP(hipStreamSynchronize(e->st));
+    return XEVE_HIP_OK;
+}
 extern "C" int xeve_hip_enc_stats(xeve_hip_enc *e, int64_t *ctu_steps, double *step_seconds, double *picture_end_seconds)
 {
     XH_REQUIRE(e);

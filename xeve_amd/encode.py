@@ -40,6 +40,93 @@ def config(w, h, qp=32, keyint=0, bframes=15, closed_gop=False, preset="medium",
     return c
 
 
+MATRICES = {"bt601": 0, "bt709": 1, "bt2020nc": 2}
+SITINGS = {"left": 0, "centre": 1}
+LAYOUTS = ("hwc", "chw")
+
+
+def color(matrix="bt709", full_range=False, siting="left"):
+    """the colour keywords of every RGB call below, checked, as a dict to pass on with ** : the matrix ("bt601", "bt709", "bt2020nc"), the range of the Y'CbCr side
+    (limited 16 .. 235 / 240 scaled to the depth, or full) and where a chroma sample sits ("left": co-sited with the even luma columns, chroma_sample_loc_type 0, what
+    decoders assume when nothing is signalled; "centre": in the middle of its 2x2 block).  THE BITSTREAM CARRIES NO COLOUR DESCRIPTION -- the reference's default streams
+    carry none and this encoder writes no VUI: whoever consumes the stream (the container, the player's settings) has to be told these three things."""
+    if matrix not in MATRICES or siting not in SITINGS:
+        raise ValueError("matrix is one of %s, siting one of %s" % (sorted(MATRICES), sorted(SITINGS)))
+    return {"matrix": matrix, "full_range": bool(full_range), "siting": siting}
+
+
+def _color(depth, **kw):
+    k = color(**kw)
+    return _lib.Color(MATRICES[k["matrix"]], int(k["full_range"]), SITINGS[k["siting"]], int(depth))
+
+
+def _rgb_desc(tensor, layout, stacked):
+    """(xeve_hip_rgb_desc of the view as it is -- tensor.stride(), no copy --, w, h, pictures)"""
+    import torch
+
+    dtypes = {torch.uint8: 0, torch.float16: 1, torch.bfloat16: 2, torch.float32: 3}
+    if layout not in LAYOUTS or tensor.dtype not in dtypes or tensor.dim() != (4 if stacked else 3):
+        raise ValueError("an RGB tensor is uint8 / float16 / bfloat16 / float32 of shape %s%s" % ("(N, " if stacked else "(", "H, W, 3) for 'hwc', 3, H, W) for 'chw'"))
+    shape, stride = list(tensor.shape), list(tensor.stride())
+    n, sp = (shape.pop(0), stride.pop(0)) if stacked else (1, 0)
+    (h, w, c), (sy, sx, sc) = (shape, stride) if layout == "hwc" else ((shape[1], shape[2], shape[0]), (stride[1], stride[2], stride[0]))
+    if c != 3:
+        raise ValueError("the component axis of an RGB tensor has length 3")
+    return _lib.RgbDesc(dtypes[tensor.dtype], 0, sx, sy, sc, sp), w, h, n
+
+
+def _on_gpu(tensor):
+    import torch
+
+    return tensor if tensor.is_cuda else tensor.to(torch.device("cuda", torch.cuda.current_device()))
+
+
+def rgb_to_yuv420(tensor, depth=10, layout="hwc", **color_kw):
+    """RGB -> the planar 4:2:0 frame BatchEncoder.push takes (xeve_hip_rgb_to_yuv420), on the tensor's GPU and torch's current stream.  tensor: (H, W, 3) / (3, H, W), or with
+    a leading axis of pictures; any view (strides are passed on, nothing is made contiguous); a host tensor is moved first.  Returns a uint8 (depth 8) or int16 (depth 10)
+    tensor of w * h * 3 / 2 samples per picture: Y, then U, then V.  color_kw: see color()"""
+    import torch
+
+    tensor = _on_gpu(tensor)
+    stacked = tensor.dim() == 4
+    desc, w, h, n = _rgb_desc(tensor, layout, stacked)
+    col = _color(depth, **color_kw)
+    per = w * h * 3 // 2
+    out = torch.empty((n, per) if stacked else (per,), dtype=torch.int16 if depth > 8 else torch.uint8, device=tensor.device)
+    with torch.cuda.device(tensor.device):
+        _lib.check(_lib.load().xeve_hip_rgb_to_yuv420(C.c_void_p(tensor.data_ptr()), C.byref(desc), C.byref(col), w, h, n, C.c_void_p(out.data_ptr()), per * out.element_size(),
+                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
+def yuv420_to_rgb(yuv, w, h, dtype=None, layout="hwc", **color_kw):
+    """the 10-bit planar 4:2:0 pictures BatchEncoder.recon_into fills -> RGB (xeve_hip_yuv420_to_rgb), on torch's current stream.  yuv: a contiguous int16 tensor of
+    w * h * 3 / 2 samples, or (N, w * h * 3 / 2) for N pictures.  Returns (H, W, 3) / (3, H, W) of dtype (torch.uint8 by default), with the leading axis when yuv has one"""
+    import torch
+
+    yuv = _on_gpu(yuv)
+    per = w * h * 3 // 2
+    if yuv.dtype != torch.int16 or not yuv.is_contiguous() or yuv.dim() not in (1, 2) or yuv.shape[-1] != per:
+        raise ValueError("yuv is a contiguous int16 tensor of w * h * 3 / 2 samples per picture")
+    stacked = yuv.dim() == 2
+    shape = (h, w, 3) if layout == "hwc" else (3, h, w)
+    out = torch.empty(((yuv.shape[0],) if stacked else ()) + shape, dtype=dtype or torch.uint8, device=yuv.device)
+    desc, _, _, n = _rgb_desc(out, layout, stacked)
+    col = _color(10, **color_kw)
+    with torch.cuda.device(yuv.device):
+        _lib.check(_lib.load().xeve_hip_yuv420_to_rgb(C.c_void_p(yuv.data_ptr()), per, C.byref(col), w, h, n, C.c_void_p(out.data_ptr()), C.byref(desc),
+                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
+def color_matrix(depth=10, **color_kw):
+    """the integer coefficients of a colour setting (xeve_hip_color_matrix; no device call): (fwd[9]: rows Y, Cb, Cr over R, G, B; (oY, oC); inv: iY, rCr, gCb, gCr, bCb)"""
+    col = _color(depth, **color_kw)
+    fwd, off, inv = (C.c_int64 * 9)(), (C.c_int64 * 2)(), (C.c_int64 * 5)()
+    _lib.check(_lib.load().xeve_hip_color_matrix(C.byref(col), fwd, off, inv))
+    return list(fwd), tuple(off), list(inv)
+
+
 class BatchEncoder:
     """enc = BatchEncoder(cfg, ngops, frames); enc.push(g, f, frame_bytes | device tensor) ...; streams = enc.encode()"""
 
@@ -76,6 +163,42 @@ class BatchEncoder:
     def push_gop(self, gop, data):
         for f in range(self.frames):
             self.push(gop, f, data[f * self.frame_bytes:(f + 1) * self.frame_bytes])
+
+    def push_rgb(self, gop, frame, tensor, layout="hwc", **color_kw):
+        """one RGB picture of w x h -- (H, W, 3) for "hwc", (3, H, W) for "chw"; uint8, float16, bfloat16 or float32 (floats in [0, 1]); any view, nothing is copied to make
+        it contiguous -- converted on the device straight into the frame's place (xeve_hip_enc_push_rgb) at the run's input depth.  A host tensor is moved to the GPU first.
+        color_kw: color()'s keywords; the stream carries no colour description, so the consumer has to be told them"""
+        import torch
+
+        tensor = _on_gpu(tensor)
+        desc, w, h, _ = _rgb_desc(tensor, layout, False)
+        if (w, h) != (self.cfg.w, self.cfg.h):
+            raise ValueError("the picture is %dx%d, the run's input %dx%d" % (w, h, self.cfg.w, self.cfg.h))
+        col = _color(10 if self.cfg.reserved[1] > 8 else 8, **color_kw)
+        torch.cuda.current_stream(tensor.device).synchronize()  # (the library converts on its own stream: whatever produced the tensor on torch's must be through)
+        _lib.check(self._L.xeve_hip_enc_push_rgb(self._h, int(gop), int(frame), C.c_void_p(tensor.data_ptr()), C.byref(desc), C.byref(col)))
+
+    def push_video_rgb(self, gop, tensor, layout="hwc", **color_kw):
+        """the run's pictures at once: the leading axis of the tensor is the frames"""
+        if tensor.shape[0] != self.frames:
+            raise ValueError("the leading axis holds %d pictures, a run %d" % (tensor.shape[0], self.frames))
+        for f in range(self.frames):
+            self.push_rgb(gop, f, tensor[f], layout, **color_kw)
+
+    def recon_rgb(self, gop, frame, dtype=None, layout="hwc", out=None, **color_kw):
+        """the reconstructed picture (config(keep_recon=True)) as RGB, converted on the device from the kept picture (xeve_hip_enc_recon_rgb): a new (H, W, 3) / (3, H, W)
+        tensor of dtype (torch.uint8 by default) on the encoder's GPU, or `out` -- any view of that shape on that GPU; complete when the call returns"""
+        import torch
+
+        if out is None:
+            out = torch.empty((self.cfg.h, self.cfg.w, 3) if layout == "hwc" else (3, self.cfg.h, self.cfg.w), dtype=dtype or torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
+        desc, w, h, _ = _rgb_desc(out, layout, False)
+        if (w, h) != (self.cfg.w, self.cfg.h) or not out.is_cuda:
+            raise ValueError("out is a %dx%d picture on the encoder's GPU" % (self.cfg.w, self.cfg.h))
+        col = _color(10, **color_kw)
+        torch.cuda.current_stream(out.device).synchronize()  # (nothing queued on torch's stream may still use the tensor)
+        _lib.check(self._L.xeve_hip_enc_recon_rgb(self._h, int(gop), int(frame), C.c_void_p(out.data_ptr()), C.byref(desc), C.byref(col)))
+        return out
 
     def begin(self):
         _lib.check(self._L.xeve_hip_enc_begin(self._h))
@@ -293,6 +416,20 @@ def encode_gops(cfg, ngops, frames, feed, free_bytes=None, max_batches=3, batch_
             for e in encs:
                 e.close()
     return out
+
+
+def encode_video_rgb(video, cfg, frames, layout="hwc", max_batches=3, **color_kw):
+    """an RGB video tensor -- (T, H, W, 3) for "hwc", (T, 3, H, W) for "chw", T a multiple of `frames` -- as T / frames closed GOPs over encode_gops; returns the joined
+    bitstream (bytes): what the reference writes for the converted sequence with --closed-gop -I frames.  color_kw: color()'s keywords (the stream does not carry them)"""
+    t = int(video.shape[0])
+    if t < frames or t % frames:
+        raise ValueError("the video's %d pictures are no multiple of %d" % (t, frames))
+
+    def feed(enc, first, n):
+        for g in range(n):
+            enc.push_video_rgb(g, video[(first + g) * frames:(first + g + 1) * frames], layout, **color_kw)
+
+    return b"".join(encode_gops(cfg, t // frames, frames, feed, max_batches=max_batches))
 
 
 def encode_file(yuv_path, out_path, cfg, gops, frames, max_batches=3, recon_path=None, stats_path=None, hash=False):

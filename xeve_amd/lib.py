@@ -57,6 +57,14 @@ class Md5Job(C.Structure):  # xeve_hip_md5_job (24 B)
     _fields_ = [("offset", C.c_int64), ("stride", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Color(C.Structure):  # xeve_hip_color (16 B)
+    _fields_ = [("matrix", C.c_int32), ("full_range", C.c_int32), ("siting", C.c_int32), ("depth", C.c_int32)]
+
+
+class RgbDesc(C.Structure):  # xeve_hip_rgb_desc (40 B); strides in elements
+    _fields_ = [("dtype", C.c_int32), ("reserved", C.c_int32), ("stride_x", C.c_int64), ("stride_y", C.c_int64), ("stride_c", C.c_int64), ("stride_pic", C.c_int64)]
+
+
 MD5_JOB_DTYPE = [("offset", "<i8"), ("stride", "<i4"), ("w", "<i4"), ("h", "<i4"), ("reserved", "<i4")]
 SIGNATURE_SEI_BYTES = 56  # XEVE_HIP_SIGNATURE_SEI_BYTES
 
@@ -292,6 +300,12 @@ FUNCTIONS = {
     "xeve_hip_md5_planes": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "xeve_hip_enc_signature": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "xeve_hip_signature_sei": (c_int, [c_int, c_void_p, c_void_p, C.c_size_t]),
+    # RGB tensors in and out: the colour conversions as leaves, their coefficients, and at the encoder's two ends
+    "xeve_hip_rgb_to_yuv420": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_i64, c_void_p]),
+    "xeve_hip_yuv420_to_rgb": (c_int, [c_void_p, c_i64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "xeve_hip_color_matrix": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "xeve_hip_enc_push_rgb": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "xeve_hip_enc_recon_rgb": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 TABLES = {
     "xeve_tbl_sad_16b_hip": FN_SAD * 64,
