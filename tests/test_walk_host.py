@@ -282,7 +282,7 @@ def test_walk_decides_every_ctu_of_the_widest_and_tallest_accepted_pictures(name
 
 @pytest.mark.parametrize("name", sorted(_enc.SATURATED_CASES))
 def test_walk_decides_every_ctu_of_saturated_content(name, walk_engine, tmp_path_factory):
-    """0 / 255 content down to QP 0 (tests/_enc.py SATURATED_CASES) through the fused walk's host side: its own quantiser and RDOQ (cu_lane.h, walk.h) and the packed
+    """0 / 255 content down to QP 0 (tests/_enc.py SATURATED_CASES) through the fused walk's host side: its own quantiser and RDOQ (walk.h) and the packed
     run / level entries with their 15 level bits, where the reference's 16-bit levels wrap -- against the reference application's bitstreams"""
     w, h, gops, frames, seed, cli, threads = _enc.SATURATED_CASES[name]
     g = _enc.golden()["batches"][name]

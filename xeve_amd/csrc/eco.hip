@@ -3,16 +3,7 @@
 // (xeve_enc.c:139) -- with xeve_hip_mode_analyze_ctu_jobs (tree.hip) a chain runs from CTU to CTU without the host, and the bytes collected here are the picture's
 // slice data (up to the pending byte and the code register, which stay in the state until the tile ends).
 #include "xh_common.h"
-// the coder's context models in LDS ([model][lane]) and, every lane function forced inline, its core in registers (cu_lane.h: XL, XL_CTX); see encode.hip
-#define XL_NCTX 72
-static __shared__ uint16_t xl_lds_ctx[XL_NCTX * 64];
-#if defined(__HIP_DEVICE_COMPILE__)
-#define XL __host__ __device__ static inline __attribute__((always_inline))
-#define XL_CTX(s, ci) xl_lds_ctx[(ci) * 64 + (threadIdx.x & 63)]
-#define XL_SINK(o) true // (every coder of this file writes: see cu_lane.h)
-#endif
-#include "eco_lane.h"
-static_assert(sizeof(((xeve_hip_sbac *)0)->ctx) == XL_NCTX * sizeof(uint16_t), "the models' LDS image");
+#include "eco_wave.h" // (the coder's context models in LDS and, every lane function forced inline, its core in registers)
 
 __global__ void __launch_bounds__(64) k_eco_ctu(const xeve_hip_ctu_data *__restrict__ ctus, xeve_hip_sbac *__restrict__ states, xl::EcoParams E, uint32_t *map_scu,
                                                 const int8_t *map_ipm, const uint8_t *map_tidx, uint32_t *map_cu_mode, long map_pic, const xeve_hip_ctu_job *__restrict__ jobs,
@@ -21,14 +12,11 @@ __global__ void __launch_bounds__(64) k_eco_ctu(const xeve_hip_ctu_data *__restr
     const int c = blockIdx.x; // one chain per wave (an arithmetic coder's control flow follows its data: chains sharing a wave run one after the other)
     if(c >= nchains) return; // (all 64 lanes run the writer in step and share the coefficient scans, eco_lane.h eco_levels)
     const xeve_hip_ctu_job J = jobs[c];
-    xl::Sbac s = states[J.sbac];
-#pragma unroll
-    for(int i = 0; i < XL_NCTX; i++) xl_lds_ctx[i * 64 + (threadIdx.x & 63)] = s.ctx[i];
+    xl::Sbac s;
+    sbac_in(s, states + J.sbac);
     xl::Sink o = {bytes + (long)c * bytes_cap, bytes_cap, 0};
     xl::eco_ctu<true>(E, s, ctus[c], map_scu + J.pic * map_pic, map_ipm + J.pic * map_pic, map_tidx + J.pic * map_pic, map_cu_mode + J.pic * map_pic, J.x, J.y, &o);
-#pragma unroll
-    for(int i = 0; i < XL_NCTX; i++) s.ctx[i] = xl_lds_ctx[i * 64 + (threadIdx.x & 63)];
-    states[J.sbac] = s;
+    sbac_out(states + J.sbac, s);
     nbytes[c] = o.n;
 }
 

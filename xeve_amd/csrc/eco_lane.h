@@ -7,10 +7,10 @@
 // The syntax is the writer's, not the rate estimate's: in P slices neither direct_mode_flag nor inter_pred_idc is coded (xeve_rdo_bit_cnt_cu_inter codes both).
 // As the CUs are written their units get what xeve_eco_unit stores (coded flag, skip flag, luma cbf flag, CU size), after the CTU's coded flags have been reset as
 // mode_analyze_lcu's tail does (xeve_mode.c:2591-2607).  Baseline (tool_admvp 0, sps_cm_init_flag 0), no delta QP, one transform block per CU (<= 64x64).
-// __host__ __device__ like cu_lane.h: tests/native builds the host side, `pytest -m "not gpu"` compares it with the oracle's xo_eco_ctu, which is pinned beside the
+// __host__ __device__ like sbac_lane.h: tests/native builds the host side, `pytest -m "not gpu"` compares it with the oracle's xo_eco_ctu, which is pinned beside the
 // reference's writer in the live encoder.
 #pragma once
-#include "cu_lane.h"
+#include "sbac_lane.h"
 
 namespace xl {
 struct EcoParams {

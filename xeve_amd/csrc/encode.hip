@@ -16,17 +16,7 @@
 #include <memory>
 #include <string>
 #include "xh_common.h"
-// The writer kernels of this file run eco_lane.h's lane code with the coder's 72 context models in LDS ([model][lane]: no bank conflicts, no scratch) and, every
-// function forced inline, the coder core (range, code, pending bytes) and the byte sink in registers.  The lane-serial form with the whole record in scratch
-// (round 2: 13 ms per CTU of noise for one chain, 346 ms per step for 2048 chains) was bound by the scratch round trip of every bin's model.
-#define XL_NCTX 72
-static __shared__ uint16_t xl_lds_ctx[XL_NCTX * 64];
-#if defined(__HIP_DEVICE_COMPILE__)
-#define XL __host__ __device__ static inline __attribute__((always_inline))
-#define XL_CTX(s, ci) xl_lds_ctx[(ci) * 64 + (threadIdx.x & 63)]
-#define XL_SINK(o) true // (every coder of this file writes: see cu_lane.h)
-#endif
-#include "eco_lane.h"
+#include "eco_wave.h" // (the writer kernels of this file run eco_lane.h's lane code with the models in LDS and the coder core in registers)
 #include "enc_host.h"
 
 using namespace xenc;
@@ -108,19 +98,6 @@ static_assert(offsetof(xeve_hip_ctu_data, pred_mode) % 16 == 0 && offsetof(xeve_
                   offsetof(xeve_hip_ctu_data, mvp_idx) % 16 == 0 && sizeof(((xeve_hip_ctu_data *)0)->split_mode) == sizeof(((xl::CtuSyntax *)0)->split_mode),
               "the walk's record: the pieces the writer takes start on 16-byte boundaries");
 static_assert(sizeof(xeve_hip_ctu_data) % 16 == 0, "CTU records are moved 16 bytes at a time");
-static_assert(sizeof(((xeve_hip_sbac *)0)->ctx) == XL_NCTX * sizeof(uint16_t), "the models' LDS image");
-__device__ __forceinline__ void sbac_in(xl::Sbac &s, const xeve_hip_sbac *__restrict__ g)
-{
-    s = *g;
-#pragma unroll
-    for(int i = 0; i < XL_NCTX; i++) xl_lds_ctx[i * 64 + (threadIdx.x & 63)] = s.ctx[i];
-}
-__device__ __forceinline__ void sbac_out(xeve_hip_sbac *__restrict__ g, xl::Sbac &s)
-{
-#pragma unroll
-    for(int i = 0; i < XL_NCTX; i++) s.ctx[i] = xl_lds_ctx[i * 64 + (threadIdx.x & 63)];
-    *g = s;
-}
 // the writer of the first pass: chain c writes the CTU it has just decided on its own coder; the bytes are kept only where they are the slice data (one chain per
 // picture: cap > 0), appended at pos[g]
 __global__ void __launch_bounds__(64) k_enc_write(const xeve_hip_ctu_data *__restrict__ ctus, xeve_hip_sbac *__restrict__ states, xl::EcoParams E, uint32_t *map_scu,
@@ -138,7 +115,7 @@ __global__ void __launch_bounds__(64) k_enc_write(const xeve_hip_ctu_data *__res
     sbac_in(s, states + J.sbac);
     // cap == 0 (a second writer pass follows: the bytes of this one are dropped): what the pass leaves is the next CTU's ENTRY STATE, and every reader of that -- the walk's
     // bit counts (xeve_sbac_bit_reset, xeve_mode.c:39-49), this writer's next CTU -- keeps the range and the context models of it and nothing else.  A code-bit count that no
-    // shift can exhaust switches the coder's byte output off (sb_shift / sb_shift_n, cu_lane.h: the boundary branch is never taken), the register fields are then
+    // shift can exhaust switches the coder's byte output off (sb_shift / sb_shift_n, sbac_lane.h: the boundary branch is never taken), the register fields are then
     // normalised so that the record does not depend on how the bins fell
     if(!cap) s.code_bits = 0x3FFFFFFFu;
     const int at = cap ? pos[J.pic] : 0;

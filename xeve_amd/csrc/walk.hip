@@ -10,9 +10,7 @@
 #define XW_NOINLINE_CODER 1
 #include "xh_common.h"
 #include "walk_setup.h"
-#ifndef XW_WG_PER_CU
 #define XW_WG_PER_CU 4
-#endif
 
 // A team's SERIAL stages (a coder job, an RDOQ scan, a per-chain decision per lane: 3 .. 60 busy lanes, ~55 % of a step's time) land on its logical threads 0 .. 63.  A CU
 // holds four teams, one wave of each on every SIMD, and a SIMD issues ONE wave instruction per 4 clocks however many waves are resident: with every team's serial lanes in
