@@ -18,7 +18,7 @@
 #include <mutex>
 #include <vector>
 
-#include "xh_common.h"
+#include "host_stage.h"
 #include "enc_plan.h"
 
 int xh_tq_init();
@@ -285,9 +285,9 @@ extern "C" int xeve_hip_prof_read(double *ms, uint64_t *launches, uint64_t *unit
 // per-thread staging for the table layer (the reference calls the tables from up to 8 pool threads,
 // lock-free: src_base/xeve_enc.c:336-365)
 // ------------------------------------------------------------------------------------------------
-[[noreturn]] static void die(const char *what)
-{
-    fprintf(stderr, "libxeve_hip: FATAL in dispatch-table call (%s): %s\n", what, xeve_hip_last_error());
+[[noreturn]] void xh_die(const char *what, bool table_call)
+{ // (host_stage.h: the one end of every entry point without a status channel, in each caller's wording)
+    fprintf(stderr, table_call ? "libxeve_hip: FATAL in dispatch-table call (%s): %s\n" : "libxeve_hip: %s failed: %s\n", what, xeve_hip_last_error());
     fflush(stderr);
     abort();
 }
@@ -296,12 +296,12 @@ extern "C" int xeve_hip_prof_read(double *ms, uint64_t *launches, uint64_t *unit
         hipError_t e_ = (expr);                                                \
         if(e_ != hipSuccess) {                                                 \
             xh_set_error("%s failed: %s", #expr, hipGetErrorString(e_));       \
-            die(__func__);                                                     \
+            xh_die(__func__, true);                                            \
         }                                                                      \
     } while(0)
-#define TBL_RC(expr)                  \
-    do {                              \
-        if((expr) != XEVE_HIP_OK) die(__func__); \
+#define TBL_RC(expr)                                     \
+    do {                                                 \
+        if((expr) != XEVE_HIP_OK) xh_die(__func__, true); \
     } while(0)
 
 namespace {
@@ -316,7 +316,7 @@ struct Stage {
     {
         if(!xh_ready()) {
             xh_set_error("dispatch table used before xeve_hip_init()");
-            die("Stage");
+            xh_die("Stage", true);
         }
         TBL_HIP(hipSetDevice(g_device.load()));
         TBL_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -428,7 +428,7 @@ static void mc_stage(const pel *at, int fx, int fy, bool hx, bool vy, int s_ref,
     const int sw = w + 16, sh = h + TAPS - 1;
     if((size_t)sw * sh * 2 > (64 << 10) || (size_t)w * h * 2 > (64 << 10)) {
         xh_set_error("mc table call %dx%d exceeds the staging tile", w, h);
-        die(__func__);
+        xh_die(__func__, true);
     }
     int16_t *tile = S.h<int16_t>(REG_A);
     memset(tile, 0, sizeof(int16_t) * (size_t)sw * sh);
@@ -547,7 +547,7 @@ template <bool FWD, int LOG2N> static void tbl_tx(void *src, void *dst, int shif
     const size_t n = (size_t)(1 << LOG2N) * line, in_b = n * (step != 1 ? 2 : 4), out_b = n * (step == 0 ? 4 : 2); // step 2: s16 -> s16 (Main)
     if(in_b > (64 << 10) || out_b > (64 << 10)) {
         xh_set_error("transform table call N=%d line=%d exceeds the staging tile", 1 << LOG2N, line);
-        die(__func__);
+        xh_die(__func__, true);
     }
     memcpy(S.h<char>(REG_A), src, in_b);
     TBL_RC(xh_tx1d(FWD, S.d<char>(REG_A), S.d<char>(REG_OUT), LOG2N, shift, line, step, S.st));
@@ -576,7 +576,7 @@ template <int TYPE, int LOG2N> static void tbl_itrans_ats(int16_t *coef, int16_t
     const size_t bytes = sizeof(int16_t) * (size_t)(1 << LOG2N) * line;
     if(bytes > (64 << 10)) {
         xh_set_error("inverse ATS table call N=%d line=%d exceeds the staging tile", 1 << LOG2N, line);
-        die(__func__);
+        xh_die(__func__, true);
     }
     memcpy(S.h<char>(REG_A), coef, bytes);
     TBL_RC(xh_itrans_ats(TYPE, LOG2N, S.d<int16_t>(REG_A), S.d<int16_t>(REG_OUT), shift, line, skip_line, skip_line_2, S.st));
@@ -591,7 +591,7 @@ template <int TYPE, int LOG2N> static void tbl_trans_ats(int16_t *block, int16_t
     const size_t bytes = sizeof(int16_t) * (size_t)(1 << LOG2N) * line;
     if(bytes > (64 << 10)) {
         xh_set_error("forward ATS table call N=%d line=%d exceeds the staging tile", 1 << LOG2N, line);
-        die(__func__);
+        xh_die(__func__, true);
     }
     memcpy(S.h<char>(REG_A), block, bytes);
     TBL_RC(xh_trans_ats(TYPE, LOG2N, S.d<int16_t>(REG_A), S.d<int16_t>(REG_OUT), shift, line, skip_line, skip_line_2, S.st));
@@ -605,7 +605,7 @@ template <int VERTICAL> static void tbl_sobel(pel *pred, int pred_stride, int *d
     g_table_calls++, g_table_calls_main++;
     if(width > 128 || height > 128 || width < 3 || height < 3) {
         xh_set_error("sobel table call %dx%d outside 3 .. 128", width, height);
-        die(__func__);
+        xh_die(__func__, true);
     }
     gather(S.h<int16_t>(REG_A), width, pred, pred_stride, width, height);
     TBL_RC(xh_sobel(VERTICAL, S.d<pel>(REG_A), width, S.d<int32_t>(REG_OUT), width, width, height, S.st));
@@ -623,7 +623,7 @@ static void tbl_ipred_ang(pel *src_le, pel *src_up, pel *src_ri, uint16_t avail_
     g_table_calls++, g_table_calls_main++;
     if(w > 128 || h > 128 || w < 1 || h < 1) {
         xh_set_error("angular prediction table call %dx%d outside 1 .. 128", w, h);
-        die(__func__);
+        xh_die(__func__, true);
     }
     const int L = w + h + 1;
     pel *lines = S.h<pel>(REG_A);
@@ -662,7 +662,7 @@ void xevem_equal_coeff_computer_hip(pel *residue, int residue_stride, int **deri
     g_table_calls++, g_table_calls_main++;
     if(width > 128 || height > 128 || width < 1 || height < 1 || (vertex_num != 2 && vertex_num != 3)) {
         xh_set_error("equal-coefficient table call %dx%d, %d vertices: outside the supported set", width, height, vertex_num);
-        die(__func__);
+        xh_die(__func__, true);
     }
     // REG_A (64 KB): the residual (dense, pitch = width), REG_B: the two derivative planes (dense), REG_MISC: the 7 x 7 accumulators
     gather(S.h<int16_t>(REG_A), width, residue, derivate_buf_stride, width, height);

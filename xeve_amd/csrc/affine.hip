@@ -335,58 +335,6 @@ extern "C" int xeve_hip_affine_mc_jobs(const xeve_hip_refpic *refp, int num_refp
     return XEVE_HIP_OK;
 }
 
-// ---- host-memory form of ONE xeve_affine_mc call (src_main/xevem_mc.c:2236-2339): what the Main-profile encoder's by-name calls can be routed to (the affine merge
-// analysis, every round of the affine gradient search, the affine bi-prediction: xevem_pinter.c:1947, 4659, 4918 -- oracle/ref_shim_affine.c does).
-// refp: table [refi * 2 + list] of HOST plane pointers (sample (0, 0)) of the pictures the CU uses; the planes extend pad_l / pad_c samples around the picture; pred_y /
-// pred_u / pred_v: HOST blocks of w * h and (w / 2) * (h / 2) samples, what the reference leaves in pred[0][Y_C / U_C / V_C].  Per calling thread one stream and one device
-// arena (grow-only): a call is the upload of the (at most two) pictures it uses, one launch, the download of three blocks.
-extern "C" int xeve_hip_affine_mc_host(int x, int y, int pic_w, int pic_h, int w, int h, const int8_t refi[2], const int16_t mv[2][3][2], const xeve_hip_refpic *refp,
-                                       int num_refp0, int num_refp1, int s_l, int s_c, int pad_l, int pad_c, xeve_hip_pel *pred_y, xeve_hip_pel *pred_u, xeve_hip_pel *pred_v,
-                                       int vertex_num, int bit_depth)
-{
-    XH_ENTER();
-    XH_REQUIRE(refi && mv && refp && pred_y && pred_u && pred_v && (vertex_num == 2 || vertex_num == 3) && pad_l >= 0 && pad_c >= 0 && s_l > 0 && s_c > 0 && pic_w > 0 && pic_h > 0);
-    XH_REQUIRE(num_refp0 >= 0 && num_refp1 >= 0 && num_refp0 <= MAXREF && num_refp1 <= MAXREF && (refi[0] < 0 || refi[0] < num_refp0) && (refi[1] < 0 || refi[1] < num_refp1) &&
-               (refi[0] >= 0 || refi[1] >= 0));
-    const size_t el = (size_t)s_l * (pic_h + 2 * pad_l), ec = (size_t)s_c * ((pic_h >> 1) + 2 * pad_c), ol = (size_t)pad_l * s_l + pad_l, oc = (size_t)pad_c * s_c + pad_c;
-    const size_t n0 = (size_t)w * h, n1 = n0 >> 2, plane = (el + 2 * ec) * sizeof(pel), o_planes = 256, o_pred = o_planes + 2 * ((plane + 255) & ~(size_t)255);
-    static thread_local XhHostArena A;
-    const int rc0 = A.ensure(o_pred + (n0 + 2 * n1) * sizeof(pel), 0);
-    if(rc0 != XEVE_HIP_OK) return rc0;
-    xeve_hip_affine_job J;
-    memset(&J, 0, sizeof(J));
-    J.x = x, J.y = y, J.vertex_num = (int8_t)vertex_num;
-    xeve_hip_refpic tab[2 * MAXREF];
-    memset(tab, 0, sizeof(tab));
-    pel *first = nullptr;
-    for(int l = 0; l < 2; l++) {
-        J.refi[l] = refi[l];
-        for(int v = 0; v < 3; v++) J.mv[l][v][0] = mv[l][v][0], J.mv[l][v][1] = mv[l][v][1];
-        if(refi[l] < 0) continue;
-        const xeve_hip_refpic &src = refp[refi[l] * 2 + l];
-        XH_REQUIRE(src.y && src.u && src.v);
-        pel *d = (pel *)(A.dev + o_planes + (size_t)l * ((plane + 255) & ~(size_t)255));
-        XH_HIP(hipMemcpyAsync(d, src.y - ol, el * sizeof(pel), hipMemcpyHostToDevice, A.st));
-        XH_HIP(hipMemcpyAsync(d + el, src.u - oc, ec * sizeof(pel), hipMemcpyHostToDevice, A.st));
-        XH_HIP(hipMemcpyAsync(d + el + ec, src.v - oc, ec * sizeof(pel), hipMemcpyHostToDevice, A.st));
-        if(!first) first = d;
-        // every picture index a list is asked to hold must be addressable: all of them alias the staged one (the job names refi[l] alone)
-        for(int r = 0; r < (l ? num_refp1 : num_refp0); r++) tab[r * 2 + l].y = d + ol, tab[r * 2 + l].u = d + el + oc, tab[r * 2 + l].v = d + el + ec + oc, tab[r * 2 + l].poc = src.poc;
-    }
-    for(int l = 0; l < 2; l++) // (a list the CU does not use: valid pointers for the table's check, never read)
-        if(refi[l] < 0)
-            for(int r = 0; r < (l ? num_refp1 : num_refp0); r++) tab[r * 2 + l].y = first + ol, tab[r * 2 + l].u = first + el + oc, tab[r * 2 + l].v = first + el + ec + oc;
-    XH_HIP(hipMemcpyAsync(A.dev, &J, sizeof(J), hipMemcpyHostToDevice, A.st));
-    pel *dp = (pel *)(A.dev + o_pred);
-    const int rc = xeve_hip_affine_mc_jobs(tab, num_refp0, num_refp1, s_l, s_c, pic_w, pic_h, (const xeve_hip_affine_job *)A.dev, 1, w, h, bit_depth, dp, dp + n0, dp + n0 + n1, A.st);
-    if(rc != XEVE_HIP_OK) return rc;
-    XH_HIP(hipMemcpyAsync(pred_y, dp, n0 * sizeof(pel), hipMemcpyDeviceToHost, A.st));
-    XH_HIP(hipMemcpyAsync(pred_u, dp + n0, n1 * sizeof(pel), hipMemcpyDeviceToHost, A.st));
-    XH_HIP(hipMemcpyAsync(pred_v, dp + n0 + n1, n1 * sizeof(pel), hipMemcpyDeviceToHost, A.st));
-    XH_HIP(hipStreamSynchronize(A.st));
-    return XEVE_HIP_OK;
-}
-
 // ---- the affine gradient search: every search of one CU size in ONE launch (a workgroup per search) ------------------------------------------------------------------------
 static int affine_me_launch(const AffMeArgs &A, int njobs, hipStream_t st)
 {
@@ -426,43 +374,14 @@ extern "C" int xeve_hip_affine_me_jobs(const xeve_hip_refpic *refp, int ntab0, i
     A.num_refp[0] = num_refp0, A.num_refp[1] = num_refp1, A.lambda_mv = lambda_mv;
     return affine_me_launch(A, njobs, (hipStream_t)stream);
 }
-
-// ---- host-memory form of ONE pinter_affine_me_gradient call (src_main/xevem_pinter.c:4290-4501): what the Main-profile encoder's pi->fn_affine_me can be bound to
-// (oracle/ref_shim_affine.c does).  ref_y: HOST luma plane (sample (0, 0)) of refp[refi][list].pic, extending pad_l samples around the picture; org: the CU's
-// first original sample with its pitch (bi: pi->org_bi, pitch w); mv: in the start vectors, out the best ones (vertex_num of them); *cost: the function's value.  Per calling
-// thread one stream and one device arena (grow-only): a call is the upload of the picture and of the CU's original, two launches, the download of the job record.
-extern "C" int xeve_hip_affine_me_host(int x, int y, int pic_w, int pic_h, int w, int h, int refi, int list, const int16_t mvp[3][2], int16_t mv[3][2], int bi, int vertex_num,
-                                       const xeve_hip_pel *ref_y, int s_l, int pad_l, const int16_t *org, int s_org, int bit_depth, uint32_t lambda_mv, int num_refp,
-                                       int mot_bits_other, uint32_t *cost)
+// ONE search on a dense original (org_block: w x h, pitch w) in the picture ref_y, all device memory: what the host-memory form launches (host_main.cpp)
+XH_LOCAL int xh_affine_me_dense(const pel *ref_y, int refi, int list, int s_l, int pic_w, int pic_h, const int16_t *org_block, xeve_hip_affine_me_job *job, int w, int h,
+                                int bit_depth, uint32_t lambda_mv, int num_refp, hipStream_t st)
 {
-    XH_ENTER();
-    XH_REQUIRE(mvp && mv && ref_y && org && cost && (vertex_num == 2 || vertex_num == 3) && pad_l >= 0 && s_l > 0 && s_org > 0 && pic_w > 0 && pic_h > 0);
-    XH_REQUIRE(refi >= 0 && refi < MAXREF && (list == 0 || list == 1) && num_refp > refi && num_refp <= 16 && xh_pow2(w) && xh_pow2(h) && w >= 16 && h >= 16 && w <= 128 && h <= 128);
-    const size_t el = (size_t)s_l * (pic_h + 2 * pad_l), ol = (size_t)pad_l * s_l + pad_l, n = (size_t)w * h;
-    const size_t o_plane = 256, o_org = o_plane + ((el * sizeof(pel) + 255) & ~(size_t)255), total = o_org + n * sizeof(int16_t);
-    static thread_local XhHostArena A;
-    const int rc0 = A.ensure(total, 0);
-    if(rc0 != XEVE_HIP_OK) return rc0;
-    xeve_hip_affine_me_job *J = reinterpret_cast<xeve_hip_affine_me_job *>(A.pin);
-    memset(J, 0, sizeof(*J));
-    J->x = x, J->y = y, J->refi = (int8_t)refi, J->list = (int8_t)list, J->bi = (int8_t)(bi != 0), J->vertex_num = (int8_t)vertex_num, J->mot_bits_other = mot_bits_other;
-    for(int v = 0; v < 3; v++)
-        for(int c = 0; c < 2; c++) J->mvp[v][c] = v < vertex_num ? mvp[v][c] : (int16_t)0, J->mv[v][c] = v < vertex_num ? mv[v][c] : (int16_t)0;
-    int16_t *ho = reinterpret_cast<int16_t *>(A.pin + o_org);
-    for(int r = 0; r < h; r++) memcpy(ho + (size_t)r * w, org + (size_t)r * s_org, (size_t)w * sizeof(int16_t));
-    XH_HIP(hipMemcpyAsync(A.dev, J, sizeof(*J), hipMemcpyHostToDevice, A.st));
-    XH_HIP(hipMemcpyAsync(A.dev + o_org, ho, n * sizeof(int16_t), hipMemcpyHostToDevice, A.st));
-    XH_HIP(hipMemcpyAsync(A.dev + o_plane, ref_y - ol, el * sizeof(pel), hipMemcpyHostToDevice, A.st));
     AffMeArgs K;
     memset(&K, 0, sizeof(K));
-    K.tab.r[refi * 2 + list].y = reinterpret_cast<const pel *>(A.dev + o_plane) + ol;
-    K.s_l = s_l, K.s_org = w, K.org = nullptr, K.org_blocks = reinterpret_cast<const int16_t *>(A.dev + o_org), K.jobs = reinterpret_cast<xeve_hip_affine_me_job *>(A.dev);
+    K.tab.r[refi * 2 + list].y = ref_y;
+    K.s_l = s_l, K.s_org = w, K.org = nullptr, K.org_blocks = org_block, K.jobs = job;
     K.pic_w = pic_w, K.pic_h = pic_h, K.w = w, K.h = h, K.bit_depth = bit_depth, K.org_dense = 1, K.num_refp[0] = K.num_refp[1] = num_refp, K.lambda_mv = lambda_mv;
-    const int rc = affine_me_launch(K, 1, A.st);
-    if(rc != XEVE_HIP_OK) return rc;
-    XH_HIP(hipMemcpyAsync(J, A.dev, sizeof(*J), hipMemcpyDeviceToHost, A.st));
-    XH_HIP(hipStreamSynchronize(A.st));
-    for(int v = 0; v < vertex_num; v++) mv[v][0] = J->mv[v][0], mv[v][1] = J->mv[v][1];
-    *cost = J->cost;
-    return XEVE_HIP_OK;
+    return affine_me_launch(K, 1, st);
 }

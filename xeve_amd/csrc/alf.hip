@@ -7,10 +7,7 @@
 //   coefficients, the class's statistics row are per block.  HBM traffic = the tile once + the outputs: all three are bandwidth-bound by construction.
 //   The statistics are integer sums (products of 12-bit sums, 64-bit accumulators) turned into doubles at the end: the reference adds the same integers into doubles
 //   sample by sample, exactly (a picture's sums stay below 2^53), so the order of accumulation cannot show.
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <vector>
 #include "alf_core.h"
 #include "xh_common.h"
 
@@ -209,113 +206,4 @@ extern "C" int xeve_hip_alf_blk_stats_jobs(int taps, const uint8_t *classifier, 
     return XEVE_HIP_OK;
 }
 
-// ---- host-memory forms with the reference's signatures (the ADAPTIVE_LOOP_FILTER object's function pointers) -----------------------------------------------------------
-namespace {
-[[noreturn]] void alf_die(const char *what)
-{ // (these signatures have no status channel, and the callers check nothing: a failure must not pass for a result)
-    fprintf(stderr, "libxeve_hip: %s failed: %s\n", what, xeve_hip_last_error());
-    abort();
-}
-struct DevBuf {
-    void *p = nullptr;
-    explicit DevBuf(size_t bytes, const char *what)
-    {
-        if(hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) xh_set_error("device allocation of %zu bytes", bytes), alf_die(what);
-    }
-    ~DevBuf() { (void)hipFree(p); }
-};
-// rows [y0, y0 + rows) x columns [x0, x0 + cols) of a host plane (pointer at its sample (0, 0), either sign of offsets) <-> a dense device buffer
-void rows_to_device(void *dev, const void *host00, long stride, int elem, int y0, int x0, int rows, int cols, const char *what)
-{
-    if(hipMemcpy2D(dev, (size_t)cols * elem, (const char *)host00 + ((long)y0 * stride + x0) * elem, (size_t)stride * elem, (size_t)cols * elem, rows, hipMemcpyHostToDevice) != hipSuccess)
-        xh_set_error("copy to the device"), alf_die(what);
-}
-void filter_host(int taps, uint8_t **classifier, pel *rec_dst, int dst_stride, const pel *rec_src, int src_stride, const xeve_hip_alf_area *blk, short *filter_set,
-                 const xeve_hip_alf_clip_range *cr, const char *what)
-{
-    if(!xh_ready()) xh_set_error("xeve_hip_init() has not been called"), alf_die(what);
-    if(!(rec_dst && rec_src && blk && filter_set && cr && blk->w > 0 && blk->h > 0 && ((blk->w | blk->h) & 3) == 0 && (taps == 5 || classifier)))
-        xh_set_error("invalid argument"), alf_die(what);
-    const int w = blk->w, h = blk->h, sw = w + 2 * MG;
-    DevBuf src((size_t)sw * (h + 2 * MG) * sizeof(pel), what), dst((size_t)w * h * sizeof(pel), what), cls((size_t)w * h, what), job(sizeof(xeve_hip_alf_filter_job), what);
-    rows_to_device(src.p, rec_src, src_stride, sizeof(pel), -MG, -MG, h + 2 * MG, sw, what);
-    if(taps == 7) { // the classifier is a table of row pointers, indexed with the area's own coordinates
-        std::vector<uint8_t> c((size_t)w * h);
-        for(int i = 0; i < h; i++) memcpy(c.data() + (size_t)i * w, classifier[blk->y + i] + blk->x, (size_t)w);
-        if(hipMemcpy(cls.p, c.data(), c.size(), hipMemcpyHostToDevice) != hipSuccess) xh_set_error("copy to the device"), alf_die(what);
-    }
-    const xeve_hip_alf_filter_job jb = {0, 0, w, h, 0, (int64_t)MG * sw + MG};
-    if(hipMemcpy(job.p, &jb, sizeof(jb), hipMemcpyHostToDevice) != hipSuccess) xh_set_error("copy to the device"), alf_die(what);
-    if(xeve_hip_alf_filter_jobs(taps, (pel *)dst.p, w, (const pel *)src.p, sw, (const uint8_t *)cls.p, w, (const xeve_hip_alf_filter_job *)job.p, 1, filter_set, cr->min, cr->max,
-                                nullptr) != XEVE_HIP_OK)
-        alf_die(what);
-    if(hipMemcpy2D(rec_dst, (size_t)dst_stride * sizeof(pel), dst.p, (size_t)w * sizeof(pel), (size_t)w * sizeof(pel), h, hipMemcpyDeviceToHost) != hipSuccess)
-        xh_set_error("copy from the device"), alf_die(what);
-}
-} // namespace
-
-extern "C" void xeve_hip_alf_derive_classification_blk_host(uint8_t **classifier, const xeve_hip_pel *src_luma, int src_stride, const xeve_hip_alf_area *blk, int shift,
-                                                            int bit_depth)
-{
-    const char *what = "xeve_hip_alf_derive_classification_blk_host";
-    (void)shift; // (unused by the reference as well, :488-493)
-    if(!xh_ready()) xh_set_error("xeve_hip_init() has not been called"), alf_die(what);
-    if(!(classifier && src_luma && blk && blk->w > 0 && blk->h > 0 && ((blk->w | blk->h) & 3) == 0)) xh_set_error("invalid argument"), alf_die(what);
-    const int w = blk->w, h = blk->h, sw = w + 2 * MG;
-    DevBuf src((size_t)sw * (h + 2 * MG) * sizeof(pel), what), cls((size_t)w * h, what);
-    rows_to_device(src.p, src_luma, src_stride, sizeof(pel), blk->y - MG, blk->x - MG, h + 2 * MG, sw, what);
-    const xeve_hip_alf_area a = {0, 0, w, h};
-    if(xeve_hip_alf_classify((uint8_t *)cls.p, w, (const pel *)src.p + (size_t)MG * sw + MG, sw, &a, bit_depth, nullptr) != XEVE_HIP_OK) alf_die(what);
-    std::vector<uint8_t> c((size_t)w * h);
-    if(hipMemcpy(c.data(), cls.p, c.size(), hipMemcpyDeviceToHost) != hipSuccess) xh_set_error("copy from the device"), alf_die(what);
-    for(int i = 0; i < h; i++) memcpy(classifier[blk->y + i] + blk->x, c.data() + (size_t)i * w, (size_t)w);
-}
-extern "C" void xeve_hip_alf_filter_blk_7_host(uint8_t **classifier, xeve_hip_pel *rec_dst, int dst_stride, const xeve_hip_pel *rec_src, int src_stride,
-                                               const xeve_hip_alf_area *blk, uint8_t comp_id, short *filter_set, const xeve_hip_alf_clip_range *clip_range)
-{
-    (void)comp_id;
-    filter_host(7, classifier, rec_dst, dst_stride, rec_src, src_stride, blk, filter_set, clip_range, "xeve_hip_alf_filter_blk_7_host");
-}
-extern "C" void xeve_hip_alf_filter_blk_5_host(uint8_t **classifier, xeve_hip_pel *rec_dst, int dst_stride, const xeve_hip_pel *rec_src, int src_stride,
-                                               const xeve_hip_alf_area *blk, uint8_t comp_id, short *filter_set, const xeve_hip_alf_clip_range *clip_range)
-{
-    (void)comp_id;
-    filter_host(5, classifier, rec_dst, dst_stride, rec_src, src_stride, blk, filter_set, clip_range, "xeve_hip_alf_filter_blk_5_host");
-}
-extern "C" void xeve_hip_alf_get_blk_stats_host(int taps, xeve_hip_alf_covariance *alf_cov, uint8_t **classifier, const xeve_hip_pel *org0, int org_stride,
-                                                const xeve_hip_pel *rec0, int rec_stride, int x, int y, int width, int height)
-{
-    const char *what = "xeve_hip_alf_get_blk_stats_host";
-    if(!xh_ready()) xh_set_error("xeve_hip_init() has not been called"), alf_die(what);
-    if(!((taps == 5 || taps == 7) && alf_cov && org0 && rec0 && width > 0 && height > 0 && ((width | height) & 3) == 0)) xh_set_error("invalid argument"), alf_die(what);
-    const int w = width, h = height, sw = w + 2 * MG, nclasses = classifier ? 25 : 1, ncoef = taps * taps / 4 + 1;
-    for(int c = 0; c < nclasses; c++)
-        if(alf_cov[c].num_coef < ncoef || !alf_cov[c].E || !alf_cov[c].y) xh_set_error("a covariance record smaller than the filter shape"), alf_die(what);
-    DevBuf rec((size_t)sw * (h + 2 * MG) * sizeof(pel), what), org((size_t)w * h * sizeof(pel), what), cls((size_t)w * h, what), job(sizeof(xeve_hip_alf_area), what);
-    DevBuf out((size_t)nclasses * (169 + 13 + 1) * sizeof(double), what);
-    rows_to_device(rec.p, rec0, rec_stride, sizeof(pel), y - MG, x - MG, h + 2 * MG, sw, what);
-    rows_to_device(org.p, org0, org_stride, sizeof(pel), y, x, h, w, what);
-    if(classifier) {
-        std::vector<uint8_t> c((size_t)w * h);
-        for(int i = 0; i < h; i++) memcpy(c.data() + (size_t)i * w, classifier[y + i] + x, (size_t)w);
-        if(hipMemcpy(cls.p, c.data(), c.size(), hipMemcpyHostToDevice) != hipSuccess) xh_set_error("copy to the device"), alf_die(what);
-    }
-    const xeve_hip_alf_area a = {0, 0, w, h};
-    if(hipMemcpy(job.p, &a, sizeof(a), hipMemcpyHostToDevice) != hipSuccess) xh_set_error("copy to the device"), alf_die(what);
-    double *dE = (double *)out.p, *dy = dE + (size_t)nclasses * 169, *dp = dy + (size_t)nclasses * 13;
-    if(xeve_hip_alf_blk_stats_jobs(taps, classifier ? (const uint8_t *)cls.p : nullptr, w, (const pel *)org.p, w, (const pel *)rec.p + (size_t)MG * sw + MG, sw,
-                                   (const xeve_hip_alf_area *)job.p, 1, dE, dy, dp, nullptr) != XEVE_HIP_OK)
-        alf_die(what);
-    std::vector<double> r((size_t)nclasses * (169 + 13 + 1));
-    if(hipMemcpy(r.data(), out.p, r.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) xh_set_error("copy from the device"), alf_die(what);
-    const double *E = r.data(), *yv = E + (size_t)nclasses * 169, *pp = yv + (size_t)nclasses * 13;
-    for(int c = 0; c < nclasses; c++) {
-        for(int k = 0; k < ncoef; k++) {
-            for(int l = k; l < ncoef; l++) alf_cov[c].E[k][l] += E[(c * 13 + k) * 13 + l];
-            alf_cov[c].y[k] += yv[c * 13 + k];
-        }
-        alf_cov[c].pix_acc += pp[c];
-        for(int k = 1; k < ncoef; k++)
-            for(int l = 0; l < k; l++) alf_cov[c].E[k][l] = alf_cov[c].E[l][k];
-    }
-}
+XH_LOCAL int xh_alf_margin() { return MG; } // (the host-memory forms stage an area with it: host_main.cpp)

@@ -14,8 +14,6 @@
 // without a host round trip.  CUs whose skip residual is below the skip_th threshold stop after the skip mode in the reference; here they
 // ride along (skip_th is 0 in every preset, so this only concerns CUs with a perfect skip prediction) and are masked in the decision.
 #include <cstring>
-#include <cstdlib>
-#include <vector>
 #include "xh_common.h"
 #include "mc_cu.h"
 
@@ -460,7 +458,7 @@ static InterLayout inter_layout(int n, int nstates, const xeve_hip_inter_params 
     return L;
 }
 
-static bool inter_params_ok(const xeve_hip_inter_params *p)
+XH_LOCAL bool inter_params_ok(const xeve_hip_inter_params *p)
 {
     const xeve_hip_rdo_params &r = p->rdo;
     return r.log2_cuw == r.log2_cuh && r.log2_cuw >= 3 && r.log2_cuw <= 6 && (r.slice_type == 0 || r.slice_type == 1) && r.tool_iqt == 0 &&
@@ -631,261 +629,4 @@ extern "C" int xeve_hip_inter_candidates(const uint32_t *map_scu, const uint8_t 
     k_inter_candidates<<<(njobs + 255) / 256, 256, 0, (hipStream_t)stream>>>(C, jobs, njobs);
     XH_HIP(hipGetLastError());
     return XEVE_HIP_OK;
-}
-
-// ---- per-thread device state of the host-memory form with resident pictures --------------------------------------------------------------
-// One stream, one device arena (job | state | result | coefficients | reconstruction | prediction | exit state | workspace) and one pinned
-// host mirror of the small records per encoder thread: a call is one upload of (job, state), the launches, one download of the outputs.
-namespace {
-// One CU's call is ~200 small dependent launches: issued one by one they cost the host 5-7 ms per CU (measured, 1280x720 and 1920x1080 encodes); the
-// whole call -- upload of (job, state), every launch, download of the results -- is therefore captured ONCE per (CU size, picture parameters) into a HIP
-// graph and replayed for every further CU of that size in the picture (all operands sit at fixed addresses of the per-thread arena; the planes are the
-// picture's resident copies).  The key is everything the launches bake in: the parameter record, the plane table, strides, the coefficient tables.
-struct HostGraph {
-    std::vector<char> key;
-    hipGraph_t        graph = nullptr;
-    hipGraphExec_t    exec  = nullptr;
-};
-struct InterHostCtx {
-    uint32_t    gen = 0;
-    hipStream_t st  = nullptr;
-    char       *dev = nullptr, *pin = nullptr;
-    size_t      dev_bytes = 0;
-    std::vector<HostGraph> graphs;
-    void drop_graphs()
-    {
-        for(auto &g : graphs) {
-            if(g.exec) (void)hipGraphExecDestroy(g.exec);
-            if(g.graph) (void)hipGraphDestroy(g.graph);
-        }
-        graphs.clear();
-    }
-    static constexpr size_t IN_BYTES = 512, OUT_BYTES = 64 << 10; // in: job + state; out: result, exit state, coef, rec, pred (64x64: 12 + 12.1 + 8 KB)
-    void release()
-    {
-        drop_graphs();
-        if(st) (void)hipStreamDestroy(st);
-        if(dev) (void)hipFree(dev);
-        if(pin) (void)hipHostFree(pin);
-        st = nullptr, dev = pin = nullptr, dev_bytes = 0;
-    }
-    int ensure(size_t ws_bytes)
-    {
-        if(gen != xh_generation()) release(), gen = xh_generation(); // the library was shut down or re-bound since
-        if(!st) XH_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        if(!pin) XH_HIP(hipHostMalloc((void **)&pin, IN_BYTES + OUT_BYTES, hipHostMallocDefault));
-        const size_t need = IN_BYTES + OUT_BYTES + 256 + ws_bytes;
-        if(dev_bytes < need) {
-            if(dev) {
-                XH_HIP(hipStreamSynchronize(st));
-                drop_graphs(); // (they hold the old arena's addresses)
-                (void)hipFree(dev);
-                dev = nullptr, dev_bytes = 0;
-            }
-            XH_HIP(hipMalloc((void **)&dev, need + (need >> 2)));
-            dev_bytes = need + (need >> 2);
-        }
-        return XEVE_HIP_OK;
-    }
-    ~InterHostCtx() { release(); }
-};
-} // namespace
-
-static int inter_host_resident(const xeve_hip_pel *const org[3], int s_org_l, int s_org_c, const xeve_hip_refpic *refp, int s_l, int s_c, int pad_l, int pad_c,
-                               const xeve_hip_sbac *state, const xeve_hip_inter_params *p, const xeve_hip_inter_job *job, const int16_t (*coef_l)[8],
-                               const int16_t (*coef_c)[4], xeve_hip_inter_result *result, int16_t *coef_y, int16_t *coef_u, int16_t *coef_v, xeve_hip_pel *rec_y,
-                               xeve_hip_pel *rec_u, xeve_hip_pel *rec_v, xeve_hip_pel *pred_y, xeve_hip_sbac *next_best)
-{
-    static thread_local InterHostCtx C;
-    const xeve_hip_rdo_params &rp = p->rdo;
-    const int idc = rp.chroma_format_idc, ws = idc <= 2, hs = idc <= 1, ncomp = idc ? 3 : 1, isb = rp.slice_type == 0;
-    const size_t n0 = (size_t)1 << (2 * rp.log2_cuw), n1 = idc ? n0 >> (ws + hs) : 0;
-    const size_t eo[3] = {(size_t)s_org_l * rp.pic_h, (size_t)s_org_c * (rp.pic_h >> hs), (size_t)s_org_c * (rp.pic_h >> hs)};
-    const size_t er[3] = {(size_t)s_l * (rp.pic_h + 2 * pad_l), (size_t)s_c * ((rp.pic_h >> hs) + 2 * pad_c), (size_t)s_c * ((rp.pic_h >> hs) + 2 * pad_c)};
-    const size_t orr[3] = {(size_t)pad_l * s_l + pad_l, (size_t)pad_c * s_c + pad_c, (size_t)pad_c * s_c + pad_c};
-    const size_t wsb = xeve_hip_pinter_analyze_cu_workspace(1, 1, p, s_org_l, s_org_c);
-    int rc = C.ensure(wsb);
-    if(rc != XEVE_HIP_OK) return rc;
-    // planes: the picture's resident copies (uploaded on first sight)
-    const pel *dorg[3] = {nullptr, nullptr, nullptr};
-    for(int c = 0; c < ncomp; c++) {
-        dorg[c] = (const pel *)xh_resident(org[c], eo[c] * sizeof(pel));
-        if(!dorg[c]) return XEVE_HIP_ERR_DEVICE;
-    }
-    xeve_hip_refpic tab[2 * MAXR];
-    memset(tab, 0, sizeof(tab));
-    const int nr[2] = {rp.num_refp[0], isb ? rp.num_refp[1] : 0};
-    for(int l = 0; l < 2; l++)
-        for(int r = 0; r < nr[l]; r++) {
-            const xeve_hip_refpic &e = refp[r * 2 + l];
-            XH_REQUIRE(e.y && (idc == 0 || (e.u && e.v)));
-            const xeve_hip_pel *hp[3] = {e.y, e.u, e.v};
-            const pel *dp[3] = {nullptr, nullptr, nullptr};
-            for(int c = 0; c < ncomp; c++) {
-                const pel *d = (const pel *)xh_resident(hp[c] - orr[c], er[c] * sizeof(pel));
-                if(!d) return XEVE_HIP_ERR_DEVICE;
-                dp[c] = d + orr[c];
-            }
-            xeve_hip_refpic &t = tab[r * 2 + l];
-            t.y = dp[0], t.u = dp[1], t.v = dp[2], t.poc = e.poc;
-        }
-    if(!isb) tab[0 * 2 + 1] = tab[0 * 2 + 0]; // (P slices never read list 1; keep the table addressable)
-    // arena layout
-    char *d = C.dev, *h = C.pin;
-    const size_t o_job = 0, o_state = 256;                                                                       // in
-    const size_t o_res = InterHostCtx::IN_BYTES, o_nb = o_res + 256, o_coef = o_nb + 256, o_rec = o_coef + (((n0 + 2 * n1) * 2 + 255) & ~(size_t)255),
-                 o_pred = o_rec + (((n0 + 2 * n1 + 16) * 2 + 255) & ~(size_t)255), o_end = o_pred + n0 * 2;     // out
-    XH_REQUIRE(o_end <= InterHostCtx::IN_BYTES + InterHostCtx::OUT_BYTES);
-    const size_t o_ws = (InterHostCtx::IN_BYTES + InterHostCtx::OUT_BYTES + 255) & ~(size_t)255;
-    xeve_hip_inter_job j0 = *job;
-    j0.sbac = 0;
-    memcpy(h + o_job, &j0, sizeof(j0)), memcpy(h + o_state, state, sizeof(*state));
-    pel *drec = (pel *)(d + o_rec);
-    auto enqueue = [&]() -> int { // the whole call on C.st
-        XH_HIP(hipMemcpyAsync(d, h, InterHostCtx::IN_BYTES, hipMemcpyHostToDevice, C.st));
-        int r = xeve_hip_pinter_analyze_cu_jobs(dorg, s_org_l, s_org_c, tab, s_l, s_c, (const xeve_hip_sbac *)(d + o_state), 1, p, (const xeve_hip_inter_job *)(d + o_job), 1,
-                                                coef_l, coef_c, (xeve_hip_inter_result *)(d + o_res), (int16_t *)(d + o_coef), drec, drec + n0 + 8, drec + n0 + n1 + 16,
-                                                (pel *)(d + o_pred), (xeve_hip_sbac *)(d + o_nb), d + o_ws, wsb, C.st);
-        if(r != XEVE_HIP_OK) return r;
-        XH_HIP(hipMemcpyAsync(h + o_res, d + o_res, o_end - o_res, hipMemcpyDeviceToHost, C.st));
-        return XEVE_HIP_OK;
-    };
-    static const int use_graph = getenv("XEVE_HIP_HOST_GRAPH") ? atoi(getenv("XEVE_HIP_HOST_GRAPH")) : 1; // developer switch (measurement)
-    if(use_graph && !xh_prof_on(XH_PROF_SEARCH) && !xh_prof_on(XH_PROF_CU_BITS)) {
-        std::vector<char> key(sizeof(*p) + sizeof(tab) + sizeof(dorg) + 4 * sizeof(int) + 2 * sizeof(void *));
-        char *k = key.data();
-        memcpy(k, p, sizeof(*p)), k += sizeof(*p);
-        memcpy(k, tab, sizeof(tab)), k += sizeof(tab);
-        memcpy(k, dorg, sizeof(dorg)), k += sizeof(dorg);
-        const int strides[4] = {s_org_l, s_org_c, s_l, s_c};
-        memcpy(k, strides, sizeof(strides)), k += sizeof(strides);
-        const void *ct[2] = {(const void *)coef_l, (const void *)coef_c};
-        memcpy(k, ct, sizeof(ct));
-        HostGraph *g = nullptr;
-        for(auto &c : C.graphs)
-            if(c.key == key) {
-                g = &c;
-                break;
-            }
-        if(!g) {
-            if(C.graphs.size() >= 64) C.drop_graphs();
-            HostGraph ng;
-            XH_HIP(hipStreamBeginCapture(C.st, hipStreamCaptureModeThreadLocal));
-            rc = enqueue();
-            const hipError_t ec = hipStreamEndCapture(C.st, &ng.graph);
-            if(rc != XEVE_HIP_OK) {
-                if(ng.graph) (void)hipGraphDestroy(ng.graph);
-                return rc;
-            }
-            XH_HIP(ec);
-            XH_HIP(hipGraphInstantiate(&ng.exec, ng.graph, nullptr, nullptr, 0));
-            ng.key = key;
-            C.graphs.push_back(std::move(ng));
-            g = &C.graphs.back();
-        }
-        XH_HIP(hipGraphLaunch(g->exec, C.st));
-    }
-    else {
-        rc = enqueue();
-        if(rc != XEVE_HIP_OK) return rc;
-    }
-    XH_HIP(hipStreamSynchronize(C.st));
-    memcpy(result, h + o_res, sizeof(*result)), memcpy(next_best, h + o_nb, sizeof(*next_best));
-    memcpy(coef_y, h + o_coef, n0 * 2), memcpy(rec_y, h + o_rec, n0 * 2);
-    if(pred_y) memcpy(pred_y, h + o_pred, n0 * 2);
-    if(idc) {
-        memcpy(coef_u, h + o_coef + n0 * 2, n1 * 2), memcpy(coef_v, h + o_coef + (n0 + n1) * 2, n1 * 2);
-        memcpy(rec_u, h + o_rec + (n0 + 8) * 2, n1 * 2), memcpy(rec_v, h + o_rec + (n0 + n1 + 16) * 2, n1 * 2);
-    }
-    return XEVE_HIP_OK;
-}
-
-// ---- host-memory form of one xeve_pinter_analyze_cu call (the table layer's style: synchronous, every plane staged per call) ----------
-// What ctx->fn_pinter_analyze_cu can be pointed at (tests/test_integration_ref.py does, through shim/xeve_hip_shim.c).  org / refp: HOST pointers to
-// sample (0, 0); the reference planes extend pad_l / pad_c samples around the picture.
-extern "C" int xeve_hip_pinter_analyze_cu_host(const xeve_hip_pel *const org[3], int s_org_l, int s_org_c, const xeve_hip_refpic *refp, int s_l, int s_c, int pad_l,
-                                               int pad_c, const xeve_hip_sbac *state, const xeve_hip_inter_params *p, const xeve_hip_inter_job *job,
-                                               const int16_t (*coef_l)[8], const int16_t (*coef_c)[4], xeve_hip_inter_result *result, int16_t *coef_y,
-                                               int16_t *coef_u, int16_t *coef_v, xeve_hip_pel *rec_y, xeve_hip_pel *rec_u, xeve_hip_pel *rec_v,
-                                               xeve_hip_pel *pred_y, xeve_hip_sbac *next_best)
-{
-    XH_ENTER();
-    XH_REQUIRE(org && org[0] && refp && state && p && job && result && coef_y && rec_y && next_best && inter_params_ok(p) && pad_l >= 0 && pad_c >= 0);
-    const xeve_hip_rdo_params &rp = p->rdo;
-    const int idc = rp.chroma_format_idc, ws = idc <= 2, hs = idc <= 1, ncomp = idc ? 3 : 1, isb = rp.slice_type == 0;
-    XH_REQUIRE(idc == 0 || (org[1] && org[2] && coef_u && coef_v && rec_u && rec_v));
-    if(xh_resident_on()) // the caller announces its pictures: planes are resident, the call moves a job and a CU's worth of results
-        return inter_host_resident(org, s_org_l, s_org_c, refp, s_l, s_c, pad_l, pad_c, state, p, job, coef_l, coef_c, result, coef_y, coef_u, coef_v, rec_y, rec_u, rec_v,
-                                   pred_y, next_best);
-    const size_t n0 = (size_t)1 << (2 * rp.log2_cuw), n1 = idc ? n0 >> (ws + hs) : 0;
-    const size_t eo[3] = {(size_t)s_org_l * rp.pic_h, (size_t)s_org_c * (rp.pic_h >> hs), (size_t)s_org_c * (rp.pic_h >> hs)};
-    const size_t er[3] = {(size_t)s_l * (rp.pic_h + 2 * pad_l), (size_t)s_c * ((rp.pic_h >> hs) + 2 * pad_c), (size_t)s_c * ((rp.pic_h >> hs) + 2 * pad_c)};
-    const size_t orr[3] = {(size_t)pad_l * s_l + pad_l, (size_t)pad_c * s_c + pad_c, (size_t)pad_c * s_c + pad_c};
-    // the pictures both lists hold (a picture may sit in both: staged once)
-    const int nr[2] = {rp.num_refp[0], isb ? rp.num_refp[1] : 0};
-    const xeve_hip_pel *uniq[2 * MAXR];
-    int nu = 0, which[2 * MAXR];
-    for(int l = 0; l < 2; l++)
-        for(int r = 0; r < nr[l]; r++) {
-            const xeve_hip_refpic &e = refp[r * 2 + l];
-            XH_REQUIRE(e.y && (idc == 0 || (e.u && e.v)));
-            int k = 0;
-            while(k < nu && uniq[k] != e.y) k++;
-            if(k == nu) uniq[nu++] = e.y;
-            which[r * 2 + l] = k;
-        }
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += al(bytes); return r; };
-    size_t o_org[3], o_ref[2 * MAXR][3];
-    for(int c = 0; c < ncomp; c++) o_org[c] = take(eo[c] * sizeof(pel));
-    for(int k = 0; k < nu; k++)
-        for(int c = 0; c < ncomp; c++) o_ref[k][c] = take(er[c] * sizeof(pel));
-    const size_t o_state = take(sizeof(xeve_hip_sbac)), o_job = take(sizeof(xeve_hip_inter_job)), o_res = take(sizeof(xeve_hip_inter_result));
-    const size_t o_coef = take((n0 + 2 * n1) * 2), o_rec = take((n0 + 2 * n1 + 16) * 2), o_pred = take(n0 * 2), o_nb = take(sizeof(xeve_hip_sbac));
-    const size_t wsb = xeve_hip_pinter_analyze_cu_workspace(1, 1, p, s_org_l, s_org_c), o_ws = take(wsb);
-    char *d = nullptr;
-    XH_HIP(hipMalloc((void **)&d, o));
-    int rc = XEVE_HIP_OK;
-    auto up = [&](size_t off, const void *src, size_t bytes) { if(rc == XEVE_HIP_OK && hipMemcpy(d + off, src, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = XEVE_HIP_ERR_DEVICE; };
-    auto down = [&](void *dst, size_t off, size_t bytes) { if(rc == XEVE_HIP_OK && hipMemcpy(dst, d + off, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = XEVE_HIP_ERR_DEVICE; };
-    for(int c = 0; c < ncomp; c++) up(o_org[c], org[c], eo[c] * sizeof(pel));
-    xeve_hip_refpic tab[2 * MAXR];
-    memset(tab, 0, sizeof(tab));
-    bool done[2 * MAXR] = {};
-    for(int l = 0; l < 2; l++)
-        for(int r = 0; r < nr[l]; r++) {
-            const xeve_hip_refpic &e = refp[r * 2 + l];
-            const int k = which[r * 2 + l];
-            const xeve_hip_pel *hp[3] = {e.y, e.u, e.v};
-            if(!done[k])
-                for(int c = 0; c < ncomp; c++) up(o_ref[k][c], hp[c] - orr[c], er[c] * sizeof(pel));
-            done[k] = true;
-            xeve_hip_refpic &t = tab[r * 2 + l];
-            t.y = (pel *)(d + o_ref[k][0]) + orr[0], t.poc = e.poc;
-            if(idc) t.u = (pel *)(d + o_ref[k][1]) + orr[1], t.v = (pel *)(d + o_ref[k][2]) + orr[2];
-        }
-    if(!isb) tab[0 * 2 + 1] = tab[0 * 2 + 0]; // (P slices never read list 1; keep the table addressable)
-    xeve_hip_inter_job j0 = *job;
-    j0.sbac = 0;
-    up(o_state, state, sizeof(*state)), up(o_job, &j0, sizeof(j0));
-    if(rc != XEVE_HIP_OK) xh_set_error("xeve_hip_pinter_analyze_cu_host: staging failed");
-    if(rc == XEVE_HIP_OK) {
-        const pel *dorg[3] = {(pel *)(d + o_org[0]), idc ? (pel *)(d + o_org[1]) : nullptr, idc ? (pel *)(d + o_org[2]) : nullptr};
-        pel *drec = (pel *)(d + o_rec);
-        rc = xeve_hip_pinter_analyze_cu_jobs(dorg, s_org_l, s_org_c, tab, s_l, s_c, (const xeve_hip_sbac *)(d + o_state), 1, p, (const xeve_hip_inter_job *)(d + o_job), 1,
-                                             coef_l, coef_c, (xeve_hip_inter_result *)(d + o_res), (int16_t *)(d + o_coef), drec, drec + n0 + 8, drec + n0 + n1 + 16,
-                                             (pel *)(d + o_pred), (xeve_hip_sbac *)(d + o_nb), d + o_ws, wsb, nullptr);
-        if(rc == XEVE_HIP_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = XEVE_HIP_ERR_DEVICE, xh_set_error("xeve_hip_pinter_analyze_cu_host: device error");
-        if(rc == XEVE_HIP_OK) {
-            down(result, o_res, sizeof(*result)), down(coef_y, o_coef, n0 * 2), down(rec_y, o_rec, n0 * 2), down(next_best, o_nb, sizeof(*next_best));
-            if(pred_y) down(pred_y, o_pred, n0 * 2);
-            if(idc) {
-                down(coef_u, o_coef + n0 * 2, n1 * 2), down(coef_v, o_coef + (n0 + n1) * 2, n1 * 2);
-                down(rec_u, o_rec + (n0 + 8) * 2, n1 * 2), down(rec_v, o_rec + (n0 + n1 + 16) * 2, n1 * 2);
-            }
-            if(rc != XEVE_HIP_OK) xh_set_error("xeve_hip_pinter_analyze_cu_host: copy back failed");
-        }
-    }
-    (void)hipFree(d);
-    return rc;
 }

@@ -500,35 +500,3 @@ int xh_me_epzs_jobs_planes(const pel *org0, int s_org, const pel *org_bi, const 
     }
     return rc;
 }
-
-
-// ---- host-memory form of one pinter_me_epzs call (the table layer's style: synchronous, planes staged per call) ------------------
-// What pi->fn_me can be pointed at (tests/test_integration_ref.py does, through shim/xeve_hip_shim.c).  org0 / ref0: sample (0, 0) of
-// the original luma plane (rows 0 .. pic_h - 1 are read) and of the padded reference luma plane (pad samples around the picture).
-extern "C" int xeve_hip_me_epzs_host(const pel *org0, int s_org, const pel *org_bi, const pel *ref0, int s_ref, int pad, int pic_h,
-                                     const xeve_hip_epzs_job *job, int log2w, int log2h, int bit_depth, const int16_t (*coef)[8],
-                                     const xeve_hip_epzs_params *params, xeve_hip_me_result *result)
-{
-    XH_ENTER();
-    XH_REQUIRE(org0 && ref0 && job && params && result && pad >= 0 && pic_h > 0);
-    const size_t eo = (size_t)s_org * pic_h, er = (size_t)s_ref * (pic_h + 2 * pad), ro = (size_t)pad * s_ref + pad, nb = (size_t)1 << (log2w + log2h);
-    const size_t wsb = xeve_hip_me_epzs_workspace(1);
-    pel *d_org = nullptr, *d_ref = nullptr, *d_bi = nullptr;
-    char *d_misc = nullptr; // job | result | workspace
-    int rc = XEVE_HIP_OK;
-    auto ok = [&](hipError_t e) { if(e != hipSuccess && rc == XEVE_HIP_OK) xh_set_error("xeve_hip_me_epzs_host: %s", hipGetErrorString(e)), rc = XEVE_HIP_ERR_DEVICE; return e == hipSuccess; };
-    ok(hipMalloc((void **)&d_org, eo * sizeof(pel))) && ok(hipMemcpy(d_org, org0, eo * sizeof(pel), hipMemcpyHostToDevice));
-    ok(hipMalloc((void **)&d_ref, er * sizeof(pel))) && ok(hipMemcpy(d_ref, ref0 - ro, er * sizeof(pel), hipMemcpyHostToDevice));
-    if(org_bi) ok(hipMalloc((void **)&d_bi, nb * sizeof(pel))) && ok(hipMemcpy(d_bi, org_bi, nb * sizeof(pel), hipMemcpyHostToDevice));
-    ok(hipMalloc((void **)&d_misc, 512 + wsb)) && ok(hipMemcpy(d_misc, job, sizeof(*job), hipMemcpyHostToDevice));
-    if(rc == XEVE_HIP_OK) {
-        xeve_hip_epzs_job j0 = *job;
-        j0.org_off = 0; // one job: its org_bi block is the whole buffer
-        ok(hipMemcpy(d_misc, &j0, sizeof(j0), hipMemcpyHostToDevice));
-        rc = xeve_hip_me_epzs_jobs(d_org, s_org, d_bi, d_ref + ro, s_ref, (const xeve_hip_epzs_job *)d_misc, 1, log2w, log2h, bit_depth, coef, params,
-                                   (xeve_hip_me_result *)(d_misc + 256), d_misc + 512, wsb, nullptr);
-        if(rc == XEVE_HIP_OK) ok(hipMemcpy(result, d_misc + 256, sizeof(*result), hipMemcpyDeviceToHost));
-    }
-    (void)hipFree(d_org), (void)hipFree(d_ref), (void)hipFree(d_bi), (void)hipFree(d_misc);
-    return rc;
-}

@@ -806,42 +806,3 @@ static int cu_bits_launch(const int16_t *coef, size_t coef_elems, const xeve_hip
     XH_HIP(hipGetLastError());
     return XEVE_HIP_OK;
 }
-
-
-// ---- host-memory form of one xeve_eco_coef call in bit-count mode (the table layer's style) -----------------------------------------
-// What ctx->fn_eco_coef can be pointed at while the encoder is counting bits (sbac->is_bitcount): the cbf flags and the coefficients of one
-// CU go through the GPU coder, continuing from *state exactly where it stands, and *state is left as the reference's coder would leave it.
-extern "C" int xeve_hip_eco_coef_host(xeve_hip_sbac *state, const int16_t *coef_y, const int16_t *coef_u, const int16_t *coef_v, int log2_cuw, int log2_cuh,
-                                      const int32_t nnz[3], int flags, int chroma_format_idc, int cm_init)
-{
-    XH_ENTER();
-    XH_REQUIRE(state && coef_y && nnz && log2_cuw >= 2 && log2_cuw <= 6 && log2_cuh >= 2 && log2_cuh <= 6 && chroma_format_idc >= 0 && chroma_format_idc <= 3);
-    XH_REQUIRE(chroma_format_idc == 0 || (coef_u && coef_v));
-    const int ws = chroma_format_idc <= 2, hs = chroma_format_idc <= 1;
-    const size_t n0 = (size_t)1 << (log2_cuw + log2_cuh), n1 = chroma_format_idc ? n0 >> (ws + hs) : 0, ne = n0 + 2 * n1;
-    xeve_hip_cu_bits_params p;
-    p.log2_cuw = log2_cuw, p.log2_cuh = log2_cuh, p.slice_type = 0, p.num_refp[0] = p.num_refp[1] = 0, p.cm_init = cm_init, p.chroma_format_idc = chroma_format_idc;
-    xeve_hip_cu_bits_job j;
-    memset(&j, 0, sizeof(j));
-    j.coef_off[0] = 0, j.coef_off[1] = (int)n0, j.coef_off[2] = (int)(n0 + n1), j.nnz[0] = nnz[0], j.nnz[1] = nnz[1], j.nnz[2] = nnz[2];
-    j.mode = XEVE_HIP_BITS_ECO_COEF, j.dir_flag = (uint8_t)(flags | XEVE_HIP_ECO_NO_RESET);
-    const size_t o_job = (ne * 2 + 255) & ~(size_t)255, o_st = o_job + 256, o_bits = o_st + 2 * 256, o_ws = o_bits + 256;
-    const size_t wsb = xeve_hip_cu_bits_workspace(1, ne);
-    char *d = nullptr;
-    XH_HIP(hipMalloc((void **)&d, o_ws + wsb));
-    int rc = XEVE_HIP_OK;
-    auto up = [&](size_t off, const void *src, size_t bytes) { if(rc == XEVE_HIP_OK && hipMemcpy(d + off, src, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = XEVE_HIP_ERR_DEVICE; };
-    up(0, coef_y, n0 * 2);
-    if(n1) up(n0 * 2, coef_u, n1 * 2), up((n0 + n1) * 2, coef_v, n1 * 2);
-    up(o_job, &j, sizeof(j)), up(o_st, state, sizeof(*state));
-    if(rc == XEVE_HIP_OK)
-        rc = xeve_hip_cu_bits_jobs((const int16_t *)d, ne, (const xeve_hip_sbac *)(d + o_st), (const xeve_hip_cu_bits_job *)(d + o_job), 1, &p, d + o_ws, wsb,
-                                   (uint32_t *)(d + o_bits), (xeve_hip_sbac *)(d + o_st + 256), nullptr);
-    else xh_set_error("xeve_hip_eco_coef_host: staging failed");
-    if(rc == XEVE_HIP_OK && hipMemcpy(state, d + o_st + 256, sizeof(*state), hipMemcpyDeviceToHost) != hipSuccess) {
-        xh_set_error("xeve_hip_eco_coef_host: copy back failed");
-        rc = XEVE_HIP_ERR_DEVICE;
-    }
-    (void)hipFree(d);
-    return rc;
-}

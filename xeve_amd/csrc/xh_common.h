@@ -7,6 +7,7 @@
 typedef int16_t pel;
 
 #define XH_WAVE 64
+#define XH_LOCAL __attribute__((visibility("hidden"))) // shared between translation units, not exported by the library
 
 // ---- DEVELOPER SWITCHES (environment, read once per process; results never depend on them: tests/test_dev_switches_gpu.py runs a reference-bitstream case under each) ------
 //   XEVE_HIP_WALK = 0 | 1 | auto, XEVE_HIP_WALK_AUTO_MAX = n       which CTU walk (composed / fused / by width: fused up to n chains, 0 since round 6); xeve_hip_walk_select
@@ -18,7 +19,7 @@ typedef int16_t pel;
 //   XEVE_HIP_ENC_SHARE = 0                                         every picture store in memory of its own (default: later stores over the frames already coded, encode.hip)
 //   XEVE_HIP_ENC_SLICE_TOLD = n                                    (the one switch results DO depend on; read at every create) the writers and the fetch are told a slice
 //                                                                  buffer of n bytes per GOP, at most the allocated size: the overflow error, reached by a test
-//   XEVE_HIP_HOST_GRAPH = 0                                        the host-memory form of the inter analysis without its per-CU graph replay
+//   XEVE_HIP_HOST_GRAPH = 0                                        the host-memory form of the inter analysis without its per-CU graph replay (host_cu.cpp)
 //   XEVE_HIP_WALK_C / _NT / _SPREAD / _DEAL / _INTER / _COUNT / _PROF / _DBG   the fused kernel's team shape, wave placement, stage profile and debug counters (walk.hip)
 // ---- error plumbing (abi.cpp) -------------------------------------------------------------
 void xh_set_error(const char *fmt, ...);
@@ -239,45 +240,6 @@ int xh_me_spel_pattern_jobs_x(const pel *org0, int s_org, const pel *org_bi, con
 int xh_me_epzs_jobs_planes(const pel *org0, int s_org, const pel *org_bi, const pel *ref0, int s_ref, const xeve_hip_epzs_job *jobs, int njobs, int log2w, int log2h,
                            int bit_depth, const int16_t (*coef)[8], const xeve_hip_epzs_params *params, const int32_t *extra_bits, xeve_hip_me_result *results,
                            void *workspace, size_t workspace_bytes, void *stream, const XhSearchPlanes *planes); // me.hip
-
-// per-thread staging of the host-memory forms that run a batched entry point on ONE unit (intra.hip, tree.hip): a stream, a pinned host buffer and a device arena
-// that grow on demand and re-create themselves after xeve_hip_shutdown / _init
-struct XhHostArena {
-    uint32_t    gen = 0;
-    hipStream_t st  = nullptr;
-    char       *dev = nullptr, *pin = nullptr;
-    size_t      dev_bytes = 0, pin_bytes = 0;
-    void release()
-    {
-        if(st) (void)hipStreamDestroy(st);
-        if(dev) (void)hipFree(dev);
-        if(pin) (void)hipHostFree(pin);
-        st = nullptr, dev = pin = nullptr, dev_bytes = pin_bytes = 0;
-    }
-    int ensure(size_t io_bytes, size_t ws_bytes)
-    {
-        if(gen != xh_generation()) release(), gen = xh_generation(); // the library was shut down or re-bound since
-        if(!st) XH_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        if(pin_bytes < io_bytes) {
-            if(pin) (void)hipHostFree(pin);
-            pin = nullptr, pin_bytes = 0;
-            XH_HIP(hipHostMalloc((void **)&pin, io_bytes + (io_bytes >> 1), hipHostMallocDefault));
-            pin_bytes = io_bytes + (io_bytes >> 1);
-        }
-        const size_t need = io_bytes + 256 + ws_bytes;
-        if(dev_bytes < need) {
-            if(dev) {
-                XH_HIP(hipStreamSynchronize(st));
-                (void)hipFree(dev);
-                dev = nullptr, dev_bytes = 0;
-            }
-            XH_HIP(hipMalloc((void **)&dev, need + (need >> 2)));
-            dev_bytes = need + (need >> 2);
-        }
-        return XEVE_HIP_OK;
-    }
-    ~XhHostArena() { release(); }
-};
 
 static inline int xh_ilog2(int v) { int l = 0; while((1 << l) < v) l++; return l; }
 static inline bool xh_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
