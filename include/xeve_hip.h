@@ -1045,6 +1045,61 @@ int xeve_hip_color_matrix(const xeve_hip_color *color, int64_t fwd[9], int64_t f
 int xeve_hip_enc_push_rgb(xeve_hip_enc *e, int gop, int frame, const void *rgb, const xeve_hip_rgb_desc *desc, const xeve_hip_color *color);
 int xeve_hip_enc_recon_rgb(xeve_hip_enc *e, int gop, int frame, void *rgb, const xeve_hip_rgb_desc *desc, const xeve_hip_color *color);
 
+/* DECODER SURFACES IN, SCALED ON THE DEVICE (xeve_amd/csrc/scale.hip, scale_core.h).  What a video decoder hands over differs from a pushed frame three ways: it is
+ * semi-planar (NV12 at 8 bits; P010 at 10 bits in the TOP bits of a 16-bit word), its rows lie a pitch apart, and it has the SOURCE's size -- the rungs of a ladder are runs
+ * of other sizes.  The leaf below turns `npics` such surfaces into the frames xeve_hip_enc_push takes in one kernel per plane; the encoder's entry point puts it in front of
+ * a run.  The reference has no counterpart: the arithmetic is this library's own, ALL INTEGER, and fully stated here, so a result is the same bits on every device and on
+ * the host.
+ * Samples: a source sample is (container >> shift) & (2^d - 1); shift is 0 for bytes and for 16-bit little-endian words that hold the sample in their low bits (whose upper
+ * bits are the caller's to keep 0: they are masked off, so every bound below holds for any bytes), 16 - d for a word that holds it in its top bits (P010: 6).  The depth d
+ * (8 | 10) is the source's AND the frame's: nothing converts between depths.
+ * Positions, per axis and per plane, sn source and dn destination samples of that plane: the centre of destination sample i in source coordinates is the exact rational
+ * p_i = ((2 i + 1) sn - dn) / (2 dn) -- luma, chroma vertically, and chroma horizontally with siting 1 (centre).  Chroma horizontally with siting 0 (left: the sample sits
+ * on the even luma column), SN and DN the LUMA widths: p_i = ((4 i + 1) SN - DN) / (4 DN).  With sn == dn both give p_i = i.
+ * Kernel: Catmull-Rom, stretched when shrinking: t = (k - p_i) min(1, dn / sn); w(t) = (3 |t|^3 - 5 |t|^2 + 2) / 2 for |t| <= 1, (-|t|^3 + 5 |t|^2 - 8 |t| + 4) / 2 for
+ * 1 < |t| < 2, 0 otherwise.  The taps of i are ALL integers k with |t| < 2 (zero weights at |t| = 1 included): at most 4 when enlarging, at most 4 sn / dn + 1 when shrinking.
+ * Coefficients at 14 fractional bits: c_k = rnd(2^14 w_k / sum w), rnd = round half away from zero of the exact rational; then the tap with the largest w (the lowest k among
+ * equals) takes what is missing, so every row sums to exactly 2^14.  The host derives them in __int128 from the integer numerators of w over the common denominator
+ * 2 D^3, D = 2 dn b (4 DN b for the left-sited form), b = sn when shrinking and 1 otherwise -- every product below 2^110, no floating point anywhere.  A tap with k outside 0 .. sn - 1 reads the clamped index
+ * and keeps its coefficient.
+ * Two passes, >> the arithmetic shift: horizontally over source rows T = (sum c s + 2^9) >> 10 (four fractional bits stay), then vertically
+ * out = clamp((sum c T + 2^17) >> 18, 0, 2^d - 1).  The definition is in unbounded integers; the kernel keeps T in 16 bits and both sums in 32, which the host PROVES for the
+ * tables in hand before any launch: with A = the largest sum of |c| over a row, |T| <= tmax = ((A_h (2^d - 1) + 2^9) >> 10) + 1 must not pass 32767 and A_v tmax + 2^17 not
+ * 2^31 - 1; a table that breaks either is refused, never wrapped.  (Catmull-Rom rows have A below 1.3 * 2^14; the bound lies at 2 * 2^14.)  An axis with sn == dn has the
+ * identity table, so a same-size call is exactly de-interleave, shift and pitch removal.
+ * Sizes: source and destination even, within 2 .. 8192 x 2 .. 4320; per axis sn <= 8 dn and dn <= 8 sn.
+ * xeve_hip_surface: layout 0 = planar (plane[0..2] = Y, U, V), 1 = semi-planar (plane[0] = Y, plane[1] = U and V interleaved, U first; plane[2] ignored); sample_bytes
+ * 1 with depth 8, 2 with depth 10 (8 bits in 16-bit words are refused); pitches and picture distances in BYTES (multiples of sample_bytes; a pitch at least the row, a distance 0 or more -- 0: one surface for every
+ * picture).  Planar with pitch = width is what xeve_hip_rgb_to_yuv420 writes: RGB at another size is the two leaves in a row.
+ * xeve_hip_scale_filter: the table of one axis.  kind 0: src_n -> dst_n samples of a PLANE (1 .. 8192 each); kind 1: the left-sited chroma columns of a picture src_n -> dst_n
+ * LUMA samples wide (even).  Rows = dst_n (kind 1: dst_n / 2); row i holds first[i] = its lowest tap and *ntaps coefficients, coef[i * *ntaps + j] for tap first[i] + j --
+ * *ntaps is the longest row's count, shorter rows end in zeros.  cap: the coefficients `coef` has room for (rows * 33 always suffice).  Host only, no device call, usable
+ * before xeve_hip_init.
+ * xeve_hip_surface_to_yuv420: `npics` surfaces of sw x sh -> frames of w x h at `depth` (== src->depth) as xeve_hip_enc_push takes them: planar Y, U, V, rows of w (w / 2)
+ * samples without padding, one byte per sample at depth 8, 16-bit little-endian at depth 10; picture p's planes lie p * pic_l / pic_c bytes behind the first, its frame
+ * p * yuv_pic_bytes behind `yuv`.  siting 0 left | 1 centre.  Everything is device memory.  Refused with XEVE_HIP_ERR_ARG before any launch: odd or oversized sizes, a ratio
+ * beyond 8, depths that differ, an unknown layout, sample size or shift, host memory, misaligned pointers, a pitch below the row, an output that overlaps the source,
+ * npics outside 1 .. 65535.  Nothing outside the described samples is read or written: the bytes between a row's end and its pitch are never read.  Three launches (Y, U, V)
+ * whatever npics is.  THE TABLES live in a cache of the library's own, keyed by (device, source length, destination length, kind): an axis is derived and uploaded on first
+ * use (tens of KB) and kept; a call all of whose axes are cached touches nothing, one that would take its device's share past 64 axes waits for that device and frees its
+ * axes; the first call after xeve_hip_shutdown or a re-bind frees them all.  Nothing is allocated unless this entry point (or the encoder's below) is called. */
+typedef struct xeve_hip_surface {
+    int32_t     layout;       /* 0 planar Y, U, V; 1 semi-planar Y + interleaved UV */
+    int32_t     sample_bytes; /* 1 | 2 */
+    int32_t     depth;        /* 8 | 10 */
+    int32_t     shift;        /* 0, or 16 - depth for a sample in the top bits of its word */
+    const void *plane[3];
+    int64_t     pitch_l, pitch_c; /* bytes between rows */
+    int64_t     pic_l, pic_c;     /* bytes between consecutive pictures' planes */
+} xeve_hip_surface;
+int xeve_hip_scale_filter(int src_n, int dst_n, int kind, int32_t *first, int16_t *coef, size_t cap, int *ntaps);
+int xeve_hip_surface_to_yuv420(const xeve_hip_surface *src, int sw, int sh, int siting, int w, int h, int depth, int npics, void *yuv, int64_t yuv_pic_bytes, void *stream);
+/* The encoder's end.  _push_surface is xeve_hip_enc_push for a decoder surface of any accepted size: converted straight into the frame's place in HBM at the run's INPUT size
+ * (cfg.w x cfg.h, also with reserved[0] bit 5) and input depth -- src->depth must equal it (8, or 10 with reserved[1] = 10), or the call is refused -- on the encoder's stream,
+ * complete when the call returns; it counts as a push.  The planes are device memory of the encoder's GPU, COMPLETE when the call is made.  No staging frame; without the
+ * call nothing is allocated or launched: footprint, max_gops and every bitstream are what they are without it. */
+int xeve_hip_enc_push_surface(xeve_hip_enc *e, int gop, int frame, const xeve_hip_surface *src, int sw, int sh, int siting);
+
 /* The application's --hash (reserved[0] bit 4): behind every picture's slice NAL unit the bitstream carries a picture-signature SEI NAL unit at the picture's temporal id
  * (xeve_pic_finish, src_base/xeve_enc.c:1255-1271; xeve_eco_signature, xeve_eco.c:300-322) -- payload type 0x10, the size byte 0x10, then the MD5 of the decoded Y, U and V
  * plane (the size byte says 16 although 48 bytes follow: reproduced as it is).  The unit is always XEVE_HIP_SIGNATURE_SEI_BYTES long, and the SEI with the option list in

@@ -853,6 +853,28 @@ extern "C" int xeve_hip_enc_recon_rgb(xeve_hip_enc *e, int gop, int frame, void 
     XH_HIP(hipStreamSynchronize(e->st));
     return XEVE_HIP_OK;
 }
+// a decoder's surface at the encoder's front end (scale.hip): scaled on the encoder's stream straight into the frame's place
+extern "C" int xeve_hip_enc_push_surface(xeve_hip_enc *e, int gop, int frame, const xeve_hip_surface *src, int sw, int sh, int siting)
+{
+    XH_ENTER();
+    XH_REQUIRE(e && src && gop >= 0 && gop < e->G && frame >= 0 && frame < e->F);
+    const int depth = e->P.input_depth > 8 ? 10 : 8;
+    if(src->depth != depth) {
+        xh_set_error("xeve_hip_enc_push_surface: src.depth (%d) is not the run's input depth (%d)", src->depth, depth);
+        return XEVE_HIP_ERR_ARG;
+    }
+    for(int p = 0; p < (src->layout == 1 ? 2 : 3); p++)
+        if(!src->plane[p] || !on_encoders_gpu(e, src->plane[p])) {
+            xh_set_error("xeve_hip_enc_push_surface: plane %d is not device memory of the encoder's GPU (%d)", p, e->device);
+            return XEVE_HIP_ERR_ARG;
+        }
+    const int rc = xeve_hip_surface_to_yuv420(src, sw, sh, siting, e->P.src_w, e->P.src_h, depth, 1, e->frames.as<uint8_t>() + ((size_t)e->pos_of_frame[frame] * e->G + gop) * e->frame_bytes,
+                                              (int64_t)e->frame_bytes, e->st);
+    if(rc != XEVE_HIP_OK) return rc;
+    XH_HIP(hipStreamSynchronize(e->st));
+    e->pushed++;
+    return XEVE_HIP_OK;
+}
 extern "C" int xeve_hip_enc_stats(xeve_hip_enc *e, int64_t *ctu_steps, double *step_seconds, double *picture_end_seconds)
 {
     XH_REQUIRE(e);

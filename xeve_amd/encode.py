@@ -127,6 +127,72 @@ def color_matrix(depth=10, **color_kw):
     return list(fwd), tuple(off), list(inv)
 
 
+def _surface(y, uv, msb_aligned, stacked):
+    """(xeve_hip_surface of the tensors as they are -- pitches and picture distances from tensor.stride(), no copy --, sw, sh, pictures, depth, the tensors kept alive).
+    y: (H, W) samples, or (N, H, W) when stacked; uv: ONE tensor (H/2, W/2, 2) of interleaved U, V pairs (NV12 / P010), or a (u, v) pair of (H/2, W/2) planes.  uint8 holds
+    8 bits; int16 / uint16 hold 10, in the low bits or with msb_aligned in the top bits"""
+    import torch
+
+    semi = hasattr(uv, "data_ptr")
+    planes = [y, uv] if semi else [y] + list(uv)
+    words = (torch.int16,) + ((torch.uint16,) if hasattr(torch, "uint16") else ())
+    lead = 1 if stacked else 0
+    if len(planes) != (2 if semi else 3) or any(p.dtype != y.dtype or p.device != y.device for p in planes) or y.dtype not in (torch.uint8,) + words:
+        raise ValueError("a surface is y and uv (one interleaved tensor or a (u, v) pair), all uint8 or all int16 / uint16, on one device")
+    if y.dim() != lead + 2 or any(p.dim() != lead + (3 if semi else 2) for p in planes[1:]):
+        raise ValueError("y is (H, W), uv (H/2, W/2, 2) or a pair of (H/2, W/2)%s" % (", each behind a leading axis of pictures" if stacked else ""))
+    es = y.element_size()
+    depth = 8 if es == 1 else 10
+    if msb_aligned and es == 1:
+        raise ValueError("msb_aligned needs 16-bit words")
+    sh, sw = int(y.shape[lead]), int(y.shape[lead + 1])
+    n = int(y.shape[0]) if stacked else 1
+    chroma = (sh // 2, sw // 2, 2) if semi else (sh // 2, sw // 2)
+    for p in planes[1:]:
+        if tuple(p.shape[lead:]) != chroma or (stacked and p.shape[0] != n):
+            raise ValueError("the chroma of a %dx%d surface is %s" % (sw, sh, "x".join(map(str, chroma))))
+    cs = planes[1].stride()
+    if y.stride(-1) != 1 or cs[-1] != 1 or (semi and cs[-2] != 2) or any(p.stride() != cs for p in planes[2:]):
+        raise ValueError("the samples of a row are neighbours in memory (an interleaved pair's as well), and u and v share their strides")
+    s = _lib.Surface(1 if semi else 0, es, depth, (16 - depth) if msb_aligned else 0)
+    for i, p in enumerate(planes):
+        s.plane[i] = p.data_ptr()
+    s.pitch_l, s.pitch_c = y.stride(lead) * es, cs[lead] * es
+    s.pic_l, s.pic_c = (y.stride(0) * es, cs[0] * es) if stacked else (0, 0)
+    return s, sw, sh, n, depth, planes
+
+
+def surface_to_yuv420(y, uv, w, h, msb_aligned=False, siting="left"):
+    """a decoder's surface -- NV12 / P010 (uv one (H/2, W/2, 2) tensor) or planar (uv a (u, v) pair), rows a pitch apart as tensor.stride() says, at the SOURCE's size -- ->
+    the planar 4:2:0 frame BatchEncoder.push takes at w x h (xeve_hip_surface_to_yuv420): de-interleaved, shifted and resampled (stretched Catmull-Rom, all integer; stated
+    in include/xeve_hip.h) in one kernel per plane, on the tensors' GPU and torch's current stream.  A leading axis of pictures on every tensor converts them at once.
+    Returns a uint8 (depth 8) or int16 (depth 10) tensor of w * h * 3 / 2 samples per picture: Y, then U, then V.  A same-size call only de-interleaves, shifts and drops
+    the pitch"""
+    import torch
+
+    if siting not in SITINGS:
+        raise ValueError("siting is one of %s" % sorted(SITINGS))
+    stacked = y.dim() == 3
+    s, sw, sh, n, depth, keep = _surface(y, uv, msb_aligned, stacked)
+    per = w * h * 3 // 2
+    out = torch.empty((n, per) if stacked else (per,), dtype=torch.int16 if depth > 8 else torch.uint8, device=y.device)
+    with torch.cuda.device(y.device):
+        _lib.check(_lib.load().xeve_hip_surface_to_yuv420(C.byref(s), sw, sh, SITINGS[siting], int(w), int(h), depth, n, C.c_void_p(out.data_ptr()), per * out.element_size(),
+                                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
+def scale_filter(src_n, dst_n, kind=0):
+    """the scaler's table of one axis (xeve_hip_scale_filter; no device call): (first, coef, ntaps) -- per destination index its lowest tap and ntaps coefficients at 14
+    fractional bits, every row summing to 16384.  kind 0: src_n -> dst_n samples of a plane; kind 1: the left-sited chroma columns of a picture src_n -> dst_n LUMA samples
+    wide (dst_n / 2 rows)"""
+    rows = max(1, int(dst_n) // 2 if kind == 1 else int(dst_n))
+    first, coef, ntaps = (C.c_int32 * rows)(), (C.c_int16 * (rows * 33))(), C.c_int()
+    _lib.check(_lib.load().xeve_hip_scale_filter(int(src_n), int(dst_n), int(kind), first, coef, rows * 33, C.byref(ntaps)))
+    t = ntaps.value
+    return list(first), [list(coef[i * t:(i + 1) * t]) for i in range(rows)], t
+
+
 class BatchEncoder:
     """enc = BatchEncoder(cfg, ngops, frames); enc.push(g, f, frame_bytes | device tensor) ...; streams = enc.encode()"""
 
@@ -177,6 +243,20 @@ class BatchEncoder:
         col = _color(10 if self.cfg.reserved[1] > 8 else 8, **color_kw)
         torch.cuda.current_stream(tensor.device).synchronize()  # (the library converts on its own stream: whatever produced the tensor on torch's must be through)
         _lib.check(self._L.xeve_hip_enc_push_rgb(self._h, int(gop), int(frame), C.c_void_p(tensor.data_ptr()), C.byref(desc), C.byref(col)))
+
+    def push_surface(self, gop, frame, y, uv, msb_aligned=False, siting="left"):
+        """one decoded picture of ANY accepted size (even, 2 .. 8192 x 2 .. 4320, within 8 : 1 of the run's per axis) -- y (H, W) with uv (H/2, W/2, 2) for NV12 / P010 or a
+        (u, v) pair; uint8 for a run of input depth 8, int16 / uint16 for depth 10 (msb_aligned: the sample in the top bits, as P010 has it); rows a pitch apart as
+        tensor.stride() says -- scaled on the device straight into the frame's place at the run's input size (xeve_hip_enc_push_surface); see surface_to_yuv420"""
+        import torch
+
+        if siting not in SITINGS:
+            raise ValueError("siting is one of %s" % sorted(SITINGS))
+        s, sw, sh, _, depth, keep = _surface(y, uv, msb_aligned, False)
+        if depth != (10 if self.cfg.reserved[1] > 8 else 8):
+            raise ValueError("a run of input depth 10 takes int16 / uint16 surfaces, one of depth 8 uint8")
+        torch.cuda.current_stream(y.device).synchronize()  # (the library converts on its own stream: whatever produced the tensors on torch's must be through)
+        _lib.check(self._L.xeve_hip_enc_push_surface(self._h, int(gop), int(frame), C.byref(s), sw, sh, SITINGS[siting]))
 
     def push_video_rgb(self, gop, tensor, layout="hwc", **color_kw):
         """the run's pictures at once: the leading axis of the tensor is the frames"""

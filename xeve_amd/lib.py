@@ -65,6 +65,11 @@ class RgbDesc(C.Structure):  # xeve_hip_rgb_desc (40 B); strides in elements
     _fields_ = [("dtype", C.c_int32), ("reserved", C.c_int32), ("stride_x", C.c_int64), ("stride_y", C.c_int64), ("stride_c", C.c_int64), ("stride_pic", C.c_int64)]
 
 
+class Surface(C.Structure):  # xeve_hip_surface (72 B); pitches and picture distances in bytes
+    _fields_ = [("layout", C.c_int32), ("sample_bytes", C.c_int32), ("depth", C.c_int32), ("shift", C.c_int32), ("plane", C.c_void_p * 3), ("pitch_l", C.c_int64),
+                ("pitch_c", C.c_int64), ("pic_l", C.c_int64), ("pic_c", C.c_int64)]
+
+
 MD5_JOB_DTYPE = [("offset", "<i8"), ("stride", "<i4"), ("w", "<i4"), ("h", "<i4"), ("reserved", "<i4")]
 SIGNATURE_SEI_BYTES = 56  # XEVE_HIP_SIGNATURE_SEI_BYTES
 
@@ -306,6 +311,10 @@ FUNCTIONS = {
     "xeve_hip_color_matrix": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "xeve_hip_enc_push_rgb": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "xeve_hip_enc_recon_rgb": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    # decoder surfaces in (NV12 / P010 / planar, pitched, any accepted size): the scaler as a leaf, its tables, and at the encoder's front end
+    "xeve_hip_scale_filter": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, C.c_size_t, c_void_p]),
+    "xeve_hip_surface_to_yuv420": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_i64, c_void_p]),
+    "xeve_hip_enc_push_surface": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int]),
 }
 TABLES = {
     "xeve_tbl_sad_16b_hip": FN_SAD * 64,
