@@ -912,7 +912,8 @@ typedef struct xeve_hip_enc_config {
     int32_t reserved[4];      /* [0] bit 0: always run the second writer pass (tests); bit 1: the application's --info 0 (no SEI with the option list); bit 2: measure every picture (xeve_hip_enc_picture_info's
                                * sse / psnr); bit 3: keep the reconstructed pictures (xeve_hip_enc_recon; w * h * 3 bytes per picture of the batch); bit 4: the application's --hash -- every picture is followed by a
                                * picture-signature SEI with the MD5 of each decoded plane, hashed on the device (xeve_hip_enc_signature; 48 bytes per picture of the batch); bit 5: w and h may be any even
-                               * size -- the picture is coded at the next multiples of 8, padded and cropped as the reference does it (see w, h); bits 8-15: --level-idc (0: 40).  [1]: the application's -d, the input's bit depth -- 0 / 8: one byte per sample;
+                               * size -- the picture is coded at the next multiples of 8, padded and cropped as the reference does it (see w, h); bit 6: measure every picture's SSIM
+                               * (xeve_hip_enc_picture_ssim; 24 bytes per picture of the batch; w and h at least 16); bits 8-15: --level-idc (0: 40).  [1]: the application's -d, the input's bit depth -- 0 / 8: one byte per sample;
                                * 10: 16-bit little-endian samples (frames pushed are twice as long).  Either way the codec works at 10 bits (--codec-bit-depth).  [2], [3]: --qp-cb-offset / --qp-cr-offset, -12 .. 12
                                * (pinned against the reference LIBRARY: the application lists the options and cannot parse them; 0 with presets slow / placebo). */
 } xeve_hip_enc_config;
@@ -993,6 +994,37 @@ int xeve_hip_frames_load(const uint8_t *frames, int64_t frame_dist, int depth, i
                          int64_t org_pic_l, int64_t org_pic_c, int npics, void *stream);
 int xeve_hip_recon_crop(const uint16_t *const rec[3], int s_rec_l, int s_rec_c, int64_t rec_pic_l, int64_t rec_pic_c, int cw, int ch, int npics, uint16_t *out, int64_t out_pic,
                         void *stream);
+
+/* SSIM BESIDE PSNR (xeve_amd/csrc/ssim.hip, ssim_core.h).  The structural similarity of the reconstructed picture and the original, per picture and plane, summed on the
+ * device at the picture's end.  The reference has no counterpart (its application prints PSNR only): the arithmetic is this library's own and fully stated here, so a
+ * result is the same bits on every device, on the host and in numpy -- an exact INTEGER per plane, from which the figure for people is one host division.
+ * Planes: the reconstruction and the original at the codec's 10 bits (an 8-bit input widened as the codec sees it, a 10-bit input as it is).  A plane of pw x ph samples is
+ * Y at w x h and U, V at w / 2 x h / 2, with w, h even and at least 16.  It is cut into 4x4 blocks from its top left, bx = pw >> 2 by by = ph >> 2 of them; samples right of
+ * column 4 bx and below row 4 by take no part.
+ * Windows: a window is a 2x2 group of adjacent blocks -- 8x8 samples on a 4-sample grid; a plane has n = (bx - 1)(by - 1) of them.
+ * Per window, over its 64 sample pairs (a, b): s1 = sum a, s2 = sum b, ss = sum (a^2 + b^2), s12 = sum a b.  C1 = 428658 = rnd(0.01^2 1023^2 64^2),
+ * C2 = 3797644 = rnd(0.03^2 1023^2 64 63).  In int64: A = 2 s1 s2 + C1, B = 2 (64 s12 - s1 s2) + C2, Cn = s1^2 + s2^2 + C1, D = 64 ss - s1^2 - s2^2 + C2; each is below 2^34
+ * in magnitude, so its conversion to double is exact.  x = ((double)A * (double)B) / ((double)Cn * (double)D): two IEEE multiplications and one IEEE division, each correctly
+ * rounded, nothing fused (the library is built with -ffp-contract=off and without fast-math).  q = (int64)floor(x * 2^30); the scaling and the floor are exact.  Cn and D
+ * are positive, |A| <= Cn and |B| <= D, so |q| <= 2^30.
+ * Per plane: Q = sum q over its windows, an exact integer (|Q| <= n 2^30 < 2^52), the same whatever the order of the adds; ssim = (double)Q / ((double)n * 2^30).
+ * Identical planes give exactly Q = n 2^30; Q is negative where the planes are anti-correlated.
+ * THE ENCODER MEASURES THE SHOWN WINDOW (reserved[0] bit 6): the input size cfg.w x cfg.h, also when bit 5 codes the picture at the next multiples of 8 -- the zeros the
+ * reference pads with are not in the figure, and Q is a function of exactly what xeve_hip_enc_recon returns and of the frames pushed.  This deliberately DIFFERS from
+ * xeve_hip_enc_picture_info's sse / psnr, which follow the application over the coded planes.  Bit 6 is independent of bits 2 and 3, changes no byte of a bitstream, and
+ * without it nothing is allocated or launched; xeve_hip_enc_create refuses it for an input below 16 in either direction.
+ * xeve_hip_enc_picture_ssim: sums[c] = Q, windows[c] = n and ssim[c] of planes Y, U, V of one picture; the validity rules and refusals of xeve_hip_enc_picture_info (a
+ * picture whose access unit is in the bitstream; may wait for the encoder's main stream; a position's pictures are read back once); a run created without bit 6 gets
+ * XEVE_HIP_ERR_ARG and a message.
+ * xeve_hip_ssim_planes, the kernel behind it as a leaf: the w x h window at the top left of `npics` stacked pictures, rec against org -- planes, strides, picture distances
+ * and alignment as xeve_hip_recon_measure takes them (luma pointers and rows 16-byte, chroma 8-byte aligned; strides and distances multiples of 8 / 4 samples, a distance 0 or more; samples
+ * at most 10 bits wide) -- into sums[npics][3].  w, h even within 16 .. 8192 x 16 .. 4320; the strides hold the window rounded up to 8 (4) samples, as xeve_hip_recon_crop's do;
+ * npics 1 .. 65535; all addressing is 64-bit.  The sums are SET: zeroed on the stream first, not added to.  Nothing but sums[0 .. 3 npics) is written; nothing outside the
+ * rows' chunks the window touches is read.  Everything is device memory; anything outside the contract -- host memory included -- is refused with XEVE_HIP_ERR_ARG before any
+ * launch.  Two launches (luma, both chroma planes) whatever npics is. */
+int xeve_hip_enc_picture_ssim(xeve_hip_enc *e, int gop, int frame, int64_t sums[3], int64_t windows[3], double ssim[3]);
+int xeve_hip_ssim_planes(const uint16_t *const rec[3], int s_rec_l, int s_rec_c, int64_t rec_pic_l, int64_t rec_pic_c, const uint16_t *const org[3], int s_org_l, int s_org_c,
+                         int64_t org_pic_l, int64_t org_pic_c, int w, int h, int npics, int64_t *sums /* [npics][3] */, void *stream);
 
 /* RGB TENSORS IN AND OUT (xeve_amd/csrc/color.hip, color_core.h).  The frames a GPU produces are RGB; the codec takes and returns planar 4:2:0 Y'CbCr.  The two leaves
  * convert between them on the device, the two encoder entry points below put them at the encoder's ends.  The reference has no counterpart (its application reads and

@@ -56,6 +56,8 @@ struct Param {
         if(h & 1) return bad("picture height must be even (4:2:0)");
         src_w = w, src_h = h, w = (int)(((long)w + 7) & ~7L), h = (int)(((long)h + 7) & ~7L);
         if(w > 8192 || h > 4320) return bad("picture larger than 8192x4320 (the coded size: width and height rounded up to multiples of 8)");
+        // (reserved[0] bit 6, SSIM per picture: measured over the INPUT size, whose chroma planes must hold a window of 8x8 samples -- include/xeve_hip.h)
+        if((c.reserved[0] & 64) && (src_w < 16 || src_h < 16)) return bad("SSIM (reserved[0] bit 6) needs a picture of at least 16x16: a chroma plane must hold one 8x8 window");
         if(qp < 0 || qp > 51 || keyint < 0 || threads < 1 || threads > 8 || fps_num <= 0 || fps_den <= 0) return bad("qp / keyint / threads / fps out of range");
         if(!(bframes == 0 || bframes == 1 || bframes == 3 || bframes == 7 || bframes == 15)) return bad("bframes must be 0, 1, 3, 7 or 15");
         if(bframes && !closed_gop && keyint % (bframes + 1) != 0) return bad("an open GOP needs keyint to be a multiple of bframes + 1");

@@ -249,6 +249,12 @@ struct xeve_hip_enc {
     bool measures() const { return (P_reserved0 & 4) != 0; }
     bool keeps_recon() const { return (P_reserved0 & 8) != 0; }
     bool hashes() const { return (P_reserved0 & 16) != 0; }
+    // SSIM beside PSNR (reserved[0] bit 6; ssim.hip): the exact sums Q of include/xeve_hip.h over the SHOWN window (src_w x src_h) of the store against `org`, taken at the
+    // same place as `sums`.  ssims: [display frame][GOP][3] on the device; h_ssims its host copy, read back per coding position when first asked for.
+    DevBuf               ssims;
+    std::vector<int64_t> h_ssims;
+    std::vector<char>    ssims_read; // per coding position
+    bool measures_ssim() const { return (P_reserved0 & 64) != 0; }
     // enc_host.h's optional member: the digests of the picture last ended, [GOP][Y, U, V]
     bool picture_digests(std::vector<uint8_t> &d)
     {
@@ -266,6 +272,10 @@ struct xeve_hip_enc {
     {
         n_served = 0, digs_frame = -1;
         au_at.assign((size_t)F * G, 0), h_sums.assign((size_t)F * G * 3, 0), sums_read.assign(F, 0);
+        if(measures_ssim()) {
+            h_ssims.assign((size_t)F * G * 3, 0), ssims_read.assign(F, 0);
+            if(!hip_ok(hipMemsetAsync(ssims.p, 0, ssims.bytes, st), "hipMemset")) return false;
+        }
         return !measures() || hip_ok(hipMemsetAsync(sums.p, 0, sums.bytes, st), "hipMemset");
     }
 
@@ -340,6 +350,7 @@ struct xeve_hip_enc {
         if(keeps_recon()) v.push_back({&kept, (size_t)G * F * pic_samples() * 2});
         if(measures()) v.push_back({&sums, (size_t)G * F * 3 * sizeof(uint64_t)});
         if(hashes()) v.push_back({&digs, (size_t)G * F * 48});
+        if(measures_ssim()) v.push_back({&ssims, (size_t)G * F * 3 * sizeof(int64_t)});
         return v;
     }
     size_t store_bytes() const { return (size_t)G * f_lcu * sizeof(xl::CtuSyntax); }
@@ -543,6 +554,13 @@ struct xeve_hip_enc {
                 return;
             if(keeps_recon() && P.cropped() &&
                !rc_ok(xeve_hip_recon_crop(r, s_l, s_c, pic_l, pic_c, P.src_w, P.src_h, G, kept.as<uint16_t>() + at * pic_samples(), (int64_t)pic_samples(), st), "xeve_hip_recon_crop"))
+                return;
+        }
+        if(measures_ssim()) { // the same place, the same planes: the SHOWN window of all G pictures (the zeros a cropped size is padded with take no part)
+            const uint16_t *r[3], *o[3];
+            for(int c = 0; c < 3; c++) r[c] = reinterpret_cast<const uint16_t *>(slot_plane(S.cur_slot, c)), o[c] = org[c].as<uint16_t>();
+            if(!rc_ok(xeve_hip_ssim_planes(r, s_l, s_c, pic_l, pic_c, o, P.w, P.w / 2, org_l, org_c, P.src_w, P.src_h, G, ssims.as<int64_t>() + (size_t)S.frame * G * 3, st),
+                      "xeve_hip_ssim_planes"))
                 return;
         }
         if(hashes()) { // the same place: the 3 * G planes of the store in ONE launch, and their 48 * G bytes to the host on the stream that made them
@@ -776,6 +794,26 @@ extern "C" int xeve_hip_enc_picture_info(xeve_hip_enc *e, int gop, int frame, xe
         out->sse[c] = e->h_sums[at + (size_t)gop * 3 + c];
         const double factor = (double)((1 << (BIT_DEPTH - 8)) * (1 << (BIT_DEPTH - 8))), mse = (double)out->sse[c] / ((double)e->P.w * e->P.h / (c ? 4 : 1));
         out->psnr[c] = mse == 0.0 ? 100. : fabs(10 * log10((255 * 255 * factor) / mse));
+    }
+    return XEVE_HIP_OK;
+}
+extern "C" int xeve_hip_enc_picture_ssim(xeve_hip_enc *e, int gop, int frame, int64_t sums[3], int64_t windows[3], double ssim[3])
+{
+    XH_ENTER();
+    XH_REQUIRE(e && sums && windows && ssim);
+    if(!e->measures_ssim()) { xh_set_error("xeve_hip_enc_picture_ssim: the run was created without reserved[0] bit 6 (SSIM)"); return XEVE_HIP_ERR_ARG; }
+    const int k = served_position(e, "xeve_hip_enc_picture_ssim", gop, frame);
+    if(k < 0) return XEVE_HIP_ERR_ARG;
+    const size_t at = (size_t)frame * e->G * 3;
+    if(!e->ssims_read[k]) { // (the G pictures of the position at once; the kernel that set them is on the main stream)
+        XH_HIP(hipMemcpyAsync(e->h_ssims.data() + at, e->ssims.as<int64_t>() + at, (size_t)e->G * 3 * sizeof(int64_t), hipMemcpyDeviceToHost, e->st));
+        XH_HIP(hipStreamSynchronize(e->st));
+        e->ssims_read[k] = 1;
+    }
+    for(int c = 0; c < 3; c++) { // the shown window's planes: n = (bx - 1)(by - 1) windows of 4x4 blocks, ssim = Q / (n 2^30)
+        const int64_t pw = c ? e->P.src_w / 2 : e->P.src_w, ph = c ? e->P.src_h / 2 : e->P.src_h;
+        sums[c] = e->h_ssims[at + (size_t)gop * 3 + c], windows[c] = ((pw >> 2) - 1) * ((ph >> 2) - 1);
+        ssim[c] = (double)sums[c] / ((double)windows[c] * 1073741824.0);
     }
     return XEVE_HIP_OK;
 }

@@ -23,19 +23,21 @@ def stats_line(p):
 
 
 def config(w, h, qp=32, keyint=0, bframes=15, closed_gop=False, preset="medium", threads=1, fps=(30, 1), ref=0, always_second_pass=False, input_depth=8, level_idc=40, sei_info=True,
-           inter_slice_type=0, qp_cb_offset=0, qp_cr_offset=0, measure=False, keep_recon=False, hash=False, crop=False):
+           inter_slice_type=0, qp_cb_offset=0, qp_cr_offset=0, measure=False, keep_recon=False, hash=False, crop=False, ssim=False):
     """the options of the reference application (xeve_app: -w -h -q -I -b --closed-gop --preset -m -z --ref -d; --inter-slice-type 0 B / 1 P, --qp-cb-offset,
     --qp-cr-offset as the reference LIBRARY takes them) as the library's configuration record.  measure: per-picture SSE / PSNR (BatchEncoder.pictures);
     keep_recon: the reconstructed pictures stay on the device (BatchEncoder.recon; w * h * 3 bytes per picture of the batch) -- neither changes the bitstream.
     hash: the application's --hash -- a 56-byte picture-signature SEI with the MD5 of each decoded plane behind every picture (BatchEncoder.signatures), hash=1 in the
     option SEI; the digests are made on the device.  crop: w and h may be any even size (960x540, 1366x768) -- the picture is coded at the next multiples of 8 with zeros
     right of the input and below it and a cropping window in the SPS, as the reference codes it; frames are pushed and recon() is handed out at w x h, PSNR and the hash
-    digests run over the coded planes as the application's do.  Without it a size that is no multiple of 8 is refused"""
+    digests run over the coded planes as the application's do.  Without it a size that is no multiple of 8 is refused.  ssim: per-picture SSIM of the SHOWN w x h window
+    (BatchEncoder.ssim; exact integer sums made on the device, stated in include/xeve_hip.h; 24 bytes per picture of the batch; w and h at least 16) -- independent of
+    measure and keep_recon, and no byte of the bitstream changes"""
     c = _lib.EncConfig()
     c.w, c.h, c.fps_num, c.fps_den, c.qp, c.keyint, c.bframes, c.closed_gop = w, h, fps[0], fps[1], qp, keyint, bframes, int(bool(closed_gop))
     c.preset, c.threads, c.inter_slice_type, c.ref = PRESETS[preset] if isinstance(preset, str) else int(preset), threads, int(inter_slice_type), ref
     c.reserved[2], c.reserved[3] = int(qp_cb_offset), int(qp_cr_offset)
-    c.reserved[0] = (1 if always_second_pass else 0) | (0 if sei_info else 2) | (4 if measure else 0) | (8 if keep_recon else 0) | (16 if hash else 0) | (32 if crop else 0) | ((int(level_idc) & 0xFF) << 8)  # (--info 0, --level-idc)
+    c.reserved[0] = (1 if always_second_pass else 0) | (0 if sei_info else 2) | (4 if measure else 0) | (8 if keep_recon else 0) | (16 if hash else 0) | (32 if crop else 0) | (64 if ssim else 0) | ((int(level_idc) & 0xFF) << 8)  # (--info 0, --level-idc)
     c.reserved[1] = int(input_depth)
     return c
 
@@ -193,6 +195,55 @@ def scale_filter(src_n, dst_n, kind=0):
     return list(first), [list(coef[i * t:(i + 1) * t]) for i in range(rows)], t
 
 
+def ssim_windows(w, h):
+    """the 8x8 windows of the planes Y, U, V of a w x h picture: (bx - 1)(by - 1) with 4x4 blocks cut from a plane's top left (include/xeve_hip.h)"""
+    return [((pw >> 2) - 1) * ((ph >> 2) - 1) for pw, ph in ((w, h), (w // 2, h // 2), (w // 2, h // 2))]
+
+
+def _ssim_operand(t, n, w, h):
+    """pictures in the recon() layout as the leaf takes planes: in place where the rows are 16-byte (8-byte) aligned as they lie, else (a width that is no multiple of 8) copied into
+    planes whose rows are: (tensors to keep alive, three addresses, (luma, chroma) strides, (luma, chroma) picture distances)"""
+    import torch
+
+    if t.dtype == torch.uint8:
+        t = t.view(torch.int16)
+    per = w * h * 3 // 2
+    if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int16 and t.numel() == n * per):
+        raise ValueError("ssim_planes takes contiguous int16 (or uint8-viewed) device tensors of w * h * 3 / 2 samples per picture")
+    nl, nc = w * h, w * h // 4
+    if w % 8 == 0:
+        return [t], [t.data_ptr(), t.data_ptr() + 2 * nl, t.data_ptr() + 2 * (nl + nc)], (w, w // 2), (per, per)
+    t, sl = t.view(n, per), (w + 7) & ~7
+    planes = [torch.zeros((n, h, sl), dtype=torch.int16, device=t.device), torch.zeros((n, h // 2, sl // 2), dtype=torch.int16, device=t.device),
+              torch.zeros((n, h // 2, sl // 2), dtype=torch.int16, device=t.device)]
+    planes[0][:, :, :w] = t[:, :nl].view(n, h, w)
+    planes[1][:, :, :w // 2] = t[:, nl:nl + nc].view(n, h // 2, w // 2)
+    planes[2][:, :, :w // 2] = t[:, nl + nc:].view(n, h // 2, w // 2)
+    return planes, [p.data_ptr() for p in planes], (sl, sl // 2), (h * sl, h // 2 * (sl // 2))
+
+
+def ssim_planes(rec, org, w, h):
+    """the SSIM sums of pictures against their originals (xeve_hip_ssim_planes; include/xeve_hip.h states the arithmetic): rec and org are device tensors holding one
+    picture, or with a leading axis several, in the layout BatchEncoder.recon() hands out -- planar Y, U, V of w x h at the codec's 10 bits, int16 (or the same bytes as
+    uint8).  Returns an int64 device tensor [3] / [n, 3] of the exact sums Q, made on torch's current stream; ssim = Q / (ssim_windows(w, h)[plane] * 2 ** 30).  A width
+    that is no multiple of 8 is first copied into planes with aligned rows"""
+    import torch
+
+    per = w * h * 3 // 2
+    stacked = rec.dim() > 1
+    n = rec.numel() * rec.element_size() // (2 * per)
+    if n < 1 or org.device != rec.device:
+        raise ValueError("rec and org hold the same number of w x h pictures on one device")
+    keep_r, pr, sr, dr = _ssim_operand(rec, n, w, h)
+    keep_o, po, so, do = _ssim_operand(org, n, w, h)
+    sums = torch.empty((n, 3), dtype=torch.int64, device=rec.device)
+    with torch.cuda.device(rec.device):
+        _lib.check(_lib.load().xeve_hip_ssim_planes((C.c_void_p * 3)(*pr), sr[0], sr[1], dr[0], dr[1], (C.c_void_p * 3)(*po), so[0], so[1], do[0], do[1], int(w), int(h), n,
+                                                    C.c_void_p(sums.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    del keep_r, keep_o  # (copies made on this stream and read on it: the allocator hands their memory out again in stream order)
+    return sums if stacked else sums[0]
+
+
 class BatchEncoder:
     """enc = BatchEncoder(cfg, ngops, frames); enc.push(g, f, frame_bytes | device tensor) ...; streams = enc.encode()"""
 
@@ -331,7 +382,20 @@ class BatchEncoder:
                "sse": [int(v) for v in p.sse], "psnr": [float(v) for v in p.psnr]}
         if self.cfg.reserved[0] & 16:  # (bytes stays the application's Bits / 8: the signature unit is not counted)
             row["md5"] = [d.hex() for d in self.signatures(gop, frame)]
+        if self.cfg.reserved[0] & 64:
+            row["ssim"] = self.ssim(gop, frame)["ssim"]
         return row
+
+    def ssim(self, gop, frame=None):
+        """the SSIM of one picture's shown w x h window (config(ssim=True)) -- xeve_hip_enc_picture_ssim: {"sums": the exact integer Q of planes Y, U, V, "windows": their
+        window counts n, "ssim": Q / (n * 2 ** 30)}, or with frame=None a list of those for every frame in display order; raises for a picture whose access unit is not in
+        the bitstream yet"""
+        out = []
+        for f in (range(self.frames) if frame is None else [int(frame)]):
+            q, n, s = (C.c_int64 * 3)(), (C.c_int64 * 3)(), (C.c_double * 3)()
+            _lib.check(self._L.xeve_hip_enc_picture_ssim(self._h, int(gop), f, q, n, s))
+            out.append({"sums": [int(v) for v in q], "windows": [int(v) for v in n], "ssim": [float(v) for v in s]})
+        return out if frame is None else out[0]
 
     def signatures(self, gop, frame=None):
         """the MD5 of the decoded Y, U and V plane (config(hash=True)) -- what the picture's signature SEI carries and hashlib.md5 gives for the planes of recon(): three
@@ -512,15 +576,17 @@ def encode_video_rgb(video, cfg, frames, layout="hwc", max_batches=3, **color_kw
     return b"".join(encode_gops(cfg, t // frames, frames, feed, max_batches=max_batches))
 
 
-def encode_file(yuv_path, out_path, cfg, gops, frames, max_batches=3, recon_path=None, stats_path=None, hash=False):
+def encode_file(yuv_path, out_path, cfg, gops, frames, max_batches=3, recon_path=None, stats_path=None, hash=False, ssim=False):
     """the whole sequence: GOP g = frames [g * frames, (g + 1) * frames) of the file; the concatenated bitstreams are what the reference writes for the same sequence
     with --closed-gop -I frames.  Sequences beyond one batch are cut into batches that run side by side (encode_gops).  recon_path: the reconstructed
     sequence, GOP after GOP in display order -- the reference's -r file of the same run; stats_path: one line per picture as the application's table prints it (POC Tid
     Ftype QP PSNR-Y PSNR-U PSNR-V Bits), every GOP in coding order.  Either switches the configuration's measure / keep_recon on for this call.  hash: the
-    application's --hash for this call (a configuration made with config(hash=True) has it already); the table's Bits stay what they are without it."""
-    if recon_path or stats_path or hash:
+    application's --hash for this call (a configuration made with config(hash=True) has it already); the table's Bits stay what they are without it.  ssim: every
+    picture's SSIM is measured in this call (config(ssim=True)) and each row of the table ends in three more columns, SSIM-Y SSIM-U SSIM-V ("%-10.6f"); without it the rows
+    are byte for byte what they are."""
+    if recon_path or stats_path or hash or ssim:
         c = _lib.EncConfig.from_buffer_copy(cfg)
-        c.reserved[0] |= (8 if recon_path else 0) | (4 if stats_path else 0) | (16 if hash else 0)
+        c.reserved[0] |= (8 if recon_path else 0) | (4 if stats_path else 0) | (16 if hash else 0) | (64 if ssim else 0)
         cfg = c
     fb = cfg.w * cfg.h * 3 // 2 * (2 if cfg.reserved[1] > 8 else 1)
     recon_file, stats_file = open(recon_path, "wb") if recon_path else None, open(stats_path, "w") if stats_path else None
@@ -531,7 +597,7 @@ def encode_file(yuv_path, out_path, cfg, gops, frames, max_batches=3, recon_path
                 recon_file.write(enc.recon(g))
             if stats_file:
                 for p in sorted(enc.pictures(g), key=lambda p: p["coding_pos"]):
-                    stats_file.write(stats_line(p) + "\n")
+                    stats_file.write(stats_line(p) + ("%-10.6f%-10.6f%-10.6f" % tuple(p["ssim"]) if ssim else "") + "\n")
 
     def feed(enc, first, n):
         with open(yuv_path, "rb") as f:

@@ -315,6 +315,9 @@ FUNCTIONS = {
     "xeve_hip_scale_filter": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, C.c_size_t, c_void_p]),
     "xeve_hip_surface_to_yuv420": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_i64, c_void_p]),
     "xeve_hip_enc_push_surface": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int]),
+    # SSIM beside PSNR: the exact per-plane sums as a leaf over stacked pictures, and per picture of the batch encoder
+    "xeve_hip_ssim_planes": (c_int, [c_void_p, c_int, c_int, c_i64, c_i64, c_void_p, c_int, c_int, c_i64, c_i64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "xeve_hip_enc_picture_ssim": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 TABLES = {
     "xeve_tbl_sad_16b_hip": FN_SAD * 64,
